@@ -32,8 +32,15 @@ Multi-GPU launch: under torch.distributed.run (WORLD_SIZE set) every rank runs t
 --gpus N` without a launcher spawns the N rank processes itself (this parent never touches the GPU) and
 exits non-zero if any rank fails.  Every rank checks that the process group has exactly N ranks.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--no-train] [--no-distill]
-                        [--no-presets] [--backend nccl|gloo] [--dry-run]
+A plain run (`python bench.py --gpus N --steps K --warmup W`) measures the headline alone: it builds the model,
+warms up, times the K steps of the exported contract and prints the result line.  `--full` adds every other
+measurement described above (train / distillation legs, validation-metrics and data-path kernels, CPU baselines,
+per-call profiles) and writes the detail file.  `--dump-outputs DIR` writes what the last timed step of the
+headline path returned (instance_masks, binary_masks) as DIR/<name>.npy in float32; the inputs are seeded, so two
+builds of the library can be compared output for output.
+
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline]
+                        [--no-train] [--no-distill] [--no-presets]] [--backend nccl|gloo] [--dry-run]
 """
 import argparse
 import json
@@ -914,6 +921,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=None, help="ranks (default: WORLD_SIZE of a launcher, else 1)")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the train / distillation legs, the validation-metrics and data-path "
+                         "kernels, the CPU baselines and the per-call profiles (default: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step of the headline path as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--no-train", action="store_true")
@@ -935,6 +947,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher + rendezvous check only (no GPU work): CPU tests of the multi-rank path")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus is not None and args.gpus > 1:
@@ -997,6 +1011,15 @@ def main():
         return
     if args.distill_only:
         args.train_only, args.no_train = True, True
+    if not (args.full or args.train_only):
+        # A plain run: the headline measurement alone, in this process (--train-only / --distill-only name legs
+        # that only a full run has, so they imply --full).
+        out = infer_bench(args, device, dtype, rank, world, dist)
+        if rank == 0:
+            print(compact_line(out), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
     # The legs run in the order --order names (default: inference, B0 train, C3, C4, distillation, unfrozen
     # distillation).  On one GPU each leg runs in a child process of its own (`bench.py --leg L`, whose JSON object this
     # process merges), so no leg inherits another's device state.  Round 6 measured every leg within 1.4 % of its
@@ -1141,6 +1164,8 @@ def _leg_in_child(leg, args):
         cmd.append("--serial")
     if args.eager_train:
         cmd.append("--eager-train")
+    if leg == "infer" and args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=None, text=True, env=env)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1148,6 +1173,27 @@ def _leg_in_child(leg, args):
         print(f"bench.py: leg {leg} failed (exit {r.returncode})", file=sys.stderr)
         sys.exit(r.returncode or 1)
     return json.loads(lines[-1])
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dirname, tensors):
+    """--dump-outputs: write each tensor as <dirname>/<name>.npy in float32 (float64 stays float64).  The
+    headline's outputs (instance_masks 12.6 MB + binary_masks 39.3 MB) fit DUMP_MAX_BYTES whole; an array that
+    would take the dump over its share of that bound is written as a fixed, seeded sample of its flattened
+    elements instead (the same indices in every run)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(tensors))
+    total = sum(t.numel() * (8 if t.dtype == torch.float64 else 4) for t in tensors.values())
+    for name, t in tensors.items():
+        t = t.detach().to("cpu")
+        a = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+        if total > DUMP_MAX_BYTES and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def infer_bench(args, device, dtype, rank, world, dist):
@@ -1170,7 +1216,8 @@ def infer_bench(args, device, dtype, rank, world, dist):
         return runner.run([(images, rois)] * k)[-1]
 
     with torch.no_grad():
-        steps(args.warmup)
+        if args.warmup > 0:
+            steps(args.warmup)
         torch.cuda.synchronize()
         if dist:
             dist.barrier()
@@ -1186,6 +1233,8 @@ def infer_bench(args, device, dtype, rank, world, dist):
         elapsed = time.perf_counter() - t0
         ops.PROBE = None
     assert inst.shape == (B * R, 1) + MASK_HW and binary.shape == (B, 1, H, W)
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        dump_outputs(args.dump_outputs, {"instance_masks": inst, "binary_masks": binary})
 
     if dist:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)

@@ -42,6 +42,43 @@ def test_gpus_must_match_the_launcher_world():
     assert "WORLD_SIZE=1" in r.stderr
 
 
+def test_full_and_dump_outputs_options_exist(tmp_path):
+    """A plain run measures the headline alone; `--full` (everything else) and `--dump-outputs DIR` are options
+    of every run.  --dry-run does no GPU work and writes nothing."""
+    r = _run(["--gpus", "1", "--dry-run", "--full", "--dump-outputs", str(tmp_path / "dump")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout.splitlines()[-1])["dry_run"]
+    assert not (tmp_path / "dump").exists()
+
+
+def test_dump_outputs_writes_float32_arrays(tmp_path, monkeypatch):
+    """--dump-outputs: one <name>.npy per output, float32 (float64 kept), values unchanged; over the size bound an
+    array becomes a sample of its elements at the same indices in every run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    masks = (torch.arange(2 * 1 * 6 * 4).reshape(2, 1, 6, 4) % 3).to(torch.uint8)
+    half = torch.linspace(-2, 2, 24).reshape(2, 1, 3, 4).to(torch.bfloat16)
+    wide = torch.linspace(0, 1, 10, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "a"), {"masks": masks, "half": half, "wide": wide})
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("masks", "half", "wide")}
+    assert got["masks"].dtype == np.float32 and got["half"].dtype == np.float32 and got["wide"].dtype == np.float64
+    assert got["masks"].shape == (2, 1, 6, 4) and np.array_equal(got["masks"], masks.numpy().astype(np.float32))
+    assert np.array_equal(got["half"], half.float().numpy()) and np.array_equal(got["wide"], wide.numpy())
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096)
+    big = torch.arange(5000, dtype=torch.float32).reshape(50, 100)
+    small = torch.arange(7, dtype=torch.float32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    b, c = np.load(tmp_path / "b" / "big.npy"), np.load(tmp_path / "c" / "big.npy")
+    assert b.dtype == np.float32 and b.shape == (512,) and np.array_equal(b, c)
+    assert len(np.unique(b)) == 512 and np.all(np.diff(b) > 0)   # distinct elements of `big`, in order
+    assert np.array_equal(np.load(tmp_path / "b" / "small.npy"), small.numpy())
+    assert b.nbytes + small.numel() * 4 <= 4096
+
+
 def _maximal_out():
     """A result object shaped like a full one-GPU run (round 5's 22.5 KB line), with every optional key present
     and long strings everywhere the detail file takes them."""
