@@ -1,0 +1,491 @@
+// Mask post-processing (include/hiseg_post.h): edge smoothing and the bilateral-filter family on f32 planes.
+//
+// One kernel shape serves every stencil chain.  A workgroup owns a tile of one plane and keeps the tile plus a
+// halo of R pixels (the "region") in LDS, in two buffers; every stage / iteration reads one buffer and writes
+// the other with a barrier in between, so a plane is read from HBM once and written once (8 bytes / pixel).
+//   resident form: the tile is the whole plane, R = 0, one workgroup per plane.  Taken when the two buffers fit
+//                  the 160 KB of LDS (H*W <= kResidentPx = 20480: the 64x48 and 128x96 instance masks).
+//   tiled form:    64x64 tiles, R = iterations * radius (summed radii for the morphological chain) <= kMaxHalo;
+//                  every tile recomputes its halo, which shrinks by one radius per stage.
+// Padding: a region pixel that lies outside the IMAGE is rewritten by every stage with the pad value of the
+// stage that reads it next (0 for a zero-padded convolution, +inf / -inf for a min / max that must not see the
+// padding), so the image border behaves as the reference's padding at every iteration, not only the first.  A
+// tap outside the REGION reads that same pad value: it only feeds pixels of the halo that the central tile never
+// depends on.  Both forms therefore compute the tile's pixels from the same values in the same order: they agree
+// bit for bit, and N iterations in one launch equal N launches of one.
+//
+// No MFMA: the kernels are LDS-read / VALU work over a bandwidth-sized stream.
+#include <math.h>
+#include "common.h"
+#include "hiseg_post.h"
+
+namespace hiseg {
+
+constexpr int kPostLds = 160 * 1024;              // bytes of LDS a workgroup may use on gfx950
+constexpr int kResidentPx = kPostLds / 8;         // two f32 buffers per pixel
+constexpr int kPostTile = 64;                     // tiled form: tile edge
+constexpr int kMaxHalo = 32;                      // (64 + 2*32)^2 * 8 B = 128 KB
+constexpr int kMaxK = 9;
+
+struct PostGeom {
+  int H, W;          // plane
+  int TH, TW;        // tile
+  int tiles_x, tiles;  // tiles per row / per plane
+  int R;             // halo
+};
+
+struct PostWeights { float w[kMaxK * kMaxK]; };
+
+// The region of this workgroup: origin in image coordinates and size.
+struct Region {
+  int y0, x0, RH, RW, H, W;
+  __device__ __forceinline__ int size() const { return RH * RW; }
+  __device__ __forceinline__ bool in_image(int ly, int lx) const {
+    return (unsigned)(y0 + ly) < (unsigned)H && (unsigned)(x0 + lx) < (unsigned)W;
+  }
+  __device__ __forceinline__ float tap(const float* buf, int ly, int lx, float pad) const {
+    return ((unsigned)ly < (unsigned)RH && (unsigned)lx < (unsigned)RW) ? buf[ly * RW + lx] : pad;
+  }
+};
+
+__device__ __forceinline__ Region region_of(const PostGeom& g, int tile) {
+  Region r;
+  r.y0 = (tile / g.tiles_x) * g.TH - g.R;
+  r.x0 = (tile % g.tiles_x) * g.TW - g.R;
+  r.RH = g.TH + 2 * g.R;
+  r.RW = g.TW + 2 * g.R;
+  r.H = g.H;
+  r.W = g.W;
+  return r;
+}
+
+// Store the central tile (clipped to the image) of `buf`; THRESH: 1.0 where value > thr, else 0.0.
+template <bool THRESH>
+__device__ __forceinline__ void store_tile(const float* buf, const Region& r, const PostGeom& g, float* out, float thr) {
+  for (int i = threadIdx.x; i < g.TH * g.TW; i += blockDim.x) {
+    const int ty = i / g.TW, tx = i - ty * g.TW;
+    const int gy = r.y0 + g.R + ty, gx = r.x0 + g.R + tx;
+    if (gy < g.H && gx < g.W) {
+      const float v = buf[(ty + g.R) * r.RW + tx + g.R];
+      out[(long long)gy * g.W + gx] = THRESH ? (v > thr ? 1.f : 0.f) : v;
+    }
+  }
+}
+
+// m*(1-e) + b*e with every operation rounded to f32 on its own, in this order (edge_smoothing.py:74).  The
+// reference's decision at a pixel whose blend is exactly 0.5 (the centre of a one-pixel line: e = sigmoid(18)
+// rounds to 1.0f) depends on it, so no contraction into an FMA and no algebraic rewrite.
+__device__ __forceinline__ float blend_f32(float m, float b, float e) {
+#pragma clang fp contract(off)
+  const float keep = m * (1.0f - e);
+  const float blur = b * e;
+  return keep + blur;
+}
+
+// 1 / (1 + exp(-x)) as torch evaluates it in f32: the accurate expf and the correctly rounded division.
+__device__ __forceinline__ float sigmoid_f32(float x) {
+#pragma clang fp contract(off)
+  return 1.0f / (1.0f + expf(-x));
+}
+
+// BinaryMaskEdgeSmoothing.forward x iterations.  MODE kEdgeClasses: the input is [B,3,H,W] scores and plane
+// p = b*3 + c is the mask argmax == c (first maximum wins); kEdgeBinarize: the mask is x > 0.5
+// (edge_smoothing.py:144).  Either is formed while the region is loaded.
+constexpr int kEdgePlain = 0, kEdgeClasses = 1, kEdgeBinarize = 2;
+template <int MODE>
+__global__ void __launch_bounds__(1024) edge_smooth_kernel(const float* __restrict__ x, float* __restrict__ out,
+                                                           PostGeom g, float threshold, float blur_strength,
+                                                           int iterations) {
+  extern __shared__ float post_lds[];
+  const long long plane = blockIdx.x / g.tiles;
+  const Region r = region_of(g, (int)(blockIdx.x % g.tiles));
+  const long long HW = (long long)g.H * g.W;
+  const int n = r.size();
+  float* a = post_lds;
+  float* b = post_lds + n;
+
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const int ly = i / r.RW, lx = i - ly * r.RW;
+    float v = 0.f;
+    if (r.in_image(ly, lx)) {
+      const long long px = (long long)(r.y0 + ly) * g.W + (r.x0 + lx);
+      if constexpr (MODE == kEdgeClasses) {
+        const float* s = x + (plane / 3) * 3 * HW + px;
+        const float s0 = s[0], s1 = s[HW], s2 = s[2 * HW];
+        int best = 0;
+        float bv = s0;
+        if (s1 > bv) { bv = s1; best = 1; }
+        if (s2 > bv) { best = 2; }
+        v = best == (int)(plane % 3) ? 1.f : 0.f;
+      } else {
+        v = x[plane * HW + px];
+        if constexpr (MODE == kEdgeBinarize) v = v > 0.5f ? 1.f : 0.f;
+      }
+    }
+    a[i] = v;
+  }
+  __syncthreads();
+
+  for (int it = 0; it < iterations; ++it) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+      const int ly = i / r.RW, lx = i - ly * r.RW;
+      float o = 0.f;
+      if (r.in_image(ly, lx)) {
+        const float c = a[i];
+        const float edge = (r.tap(a, ly - 1, lx, 0.f) + r.tap(a, ly + 1, lx, 0.f)) +
+                           (r.tap(a, ly, lx - 1, 0.f) + r.tap(a, ly, lx + 1, 0.f));
+        const float corner = (r.tap(a, ly - 1, lx - 1, 0.f) + r.tap(a, ly - 1, lx + 1, 0.f)) +
+                             (r.tap(a, ly + 1, lx - 1, 0.f) + r.tap(a, ly + 1, lx + 1, 0.f));
+        const float lap = 8.f * c - (edge + corner);
+        const float blurred = 0.25f * c + (0.125f * edge + 0.0625f * corner);
+        const float e = sigmoid_f32(fabsf(lap) * blur_strength);
+        o = blend_f32(c, blurred, e) > threshold ? 1.f : 0.f;
+      }
+      b[i] = o;
+    }
+    __syncthreads();
+    float* t = a; a = b; b = t;
+  }
+  store_tile<false>(a, r, g, out + plane * HW, 0.f);
+}
+
+// x <- w*f + (1-w)*x with f = G*x, w = exp(-max(G*x^2 - f^2, 0) * gain); G = K x K weights, zero padding.
+template <int K>
+__global__ void __launch_bounds__(1024) var_gated_blur_kernel(const float* __restrict__ x, float* __restrict__ out,
+                                                              PostGeom g, PostWeights wt, float gain, int clamp_input,
+                                                              int threshold_output, float threshold, int iterations) {
+  extern __shared__ float post_lds[];
+  constexpr int P = K / 2;
+  const long long plane = blockIdx.x / g.tiles;
+  const Region r = region_of(g, (int)(blockIdx.x % g.tiles));
+  const long long HW = (long long)g.H * g.W;
+  const int n = r.size();
+  float* a = post_lds;
+  float* b = post_lds + n;
+
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const int ly = i / r.RW, lx = i - ly * r.RW;
+    float v = 0.f;
+    if (r.in_image(ly, lx)) {
+      v = x[plane * HW + (long long)(r.y0 + ly) * g.W + (r.x0 + lx)];
+      if (clamp_input) v = fminf(fmaxf(v, 0.f), 1.f);
+    }
+    a[i] = v;
+  }
+  __syncthreads();
+
+  for (int it = 0; it < iterations; ++it) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+      const int ly = i / r.RW, lx = i - ly * r.RW;
+      float o = 0.f;
+      if (r.in_image(ly, lx)) {
+        float f = 0.f, q = 0.f;
+#pragma unroll
+        for (int dy = 0; dy < K; ++dy) {
+#pragma unroll
+          for (int dx = 0; dx < K; ++dx) {
+            const float v = r.tap(a, ly + dy - P, lx + dx - P, 0.f);
+            const float wv = wt.w[dy * K + dx] * v;
+            f += wv;
+            q = fmaf(wv, v, q);
+          }
+        }
+        const float var = fmaxf(q - f * f, 0.f);
+        const float w = expf(-var * gain);
+        o = w * f + (1.f - w) * a[i];
+      }
+      b[i] = o;
+    }
+    __syncthreads();
+    float* t = a; a = b; b = t;
+  }
+  if (threshold_output) store_tile<true>(a, r, g, out + plane * HW, threshold);
+  else store_tile<false>(a, r, g, out + plane * HW, 0.f);
+}
+
+// One min (MAX = false) or max stage over an m x m window that never sees the padding: pixels outside the image
+// hold the identity of the stage (+inf / -inf), written by the stage before as `next_pad`.
+template <bool MAX>
+__device__ __forceinline__ void minmax_stage(const float* a, float* b, const Region& r, int rad, float next_pad) {
+  const float ident = MAX ? -INFINITY : INFINITY;
+  const int n = r.size();
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const int ly = i / r.RW, lx = i - ly * r.RW;
+    float o = next_pad;
+    if (r.in_image(ly, lx)) {
+      float m = ident;
+      for (int dy = -rad; dy <= rad; ++dy)
+        for (int dx = -rad; dx <= rad; ++dx) {
+          const float v = r.tap(a, ly + dy, lx + dx, ident);
+          m = MAX ? fmaxf(m, v) : fminf(m, v);
+        }
+      o = m;
+    }
+    b[i] = o;
+  }
+  __syncthreads();
+}
+
+// MorphologicalBilateralFilter.forward: clamp, open (min, max), K x K Gaussian with zero padding, close (max,
+// min), > 0.5.
+template <int K>
+__global__ void __launch_bounds__(1024) morph_bilateral_kernel(const float* __restrict__ x, float* __restrict__ out,
+                                                               PostGeom g, PostWeights wt, int morph_rad) {
+  extern __shared__ float post_lds[];
+  constexpr int P = K / 2;
+  const long long plane = blockIdx.x / g.tiles;
+  const Region r = region_of(g, (int)(blockIdx.x % g.tiles));
+  const long long HW = (long long)g.H * g.W;
+  const int n = r.size();
+  float* a = post_lds;
+  float* b = post_lds + n;
+
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const int ly = i / r.RW, lx = i - ly * r.RW;
+    float v = INFINITY;
+    if (r.in_image(ly, lx))
+      v = fminf(fmaxf(x[plane * HW + (long long)(r.y0 + ly) * g.W + (r.x0 + lx)], 0.f), 1.f);
+    a[i] = v;
+  }
+  __syncthreads();
+  minmax_stage<false>(a, b, r, morph_rad, -INFINITY);   // erode
+  minmax_stage<true>(b, a, r, morph_rad, 0.f);          // dilate -> opened, zero padded for the convolution
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const int ly = i / r.RW, lx = i - ly * r.RW;
+    float o = -INFINITY;
+    if (r.in_image(ly, lx)) {
+      float f = 0.f;
+#pragma unroll
+      for (int dy = 0; dy < K; ++dy) {
+#pragma unroll
+        for (int dx = 0; dx < K; ++dx) f = fmaf(wt.w[dy * K + dx], r.tap(a, ly + dy - P, lx + dx - P, 0.f), f);
+      }
+      o = f;
+    }
+    b[i] = o;
+  }
+  __syncthreads();
+  minmax_stage<true>(b, a, r, morph_rad, INFINITY);     // dilate
+  minmax_stage<false>(a, b, r, morph_rad, 0.f);         // erode -> closed
+  store_tile<true>(b, r, g, out + plane * HW, 0.5f);
+}
+
+// BilateralFilter.forward: reflect padding, weight = spatial * exp(-(p - c)^2 * inv2sr), sum(p*w) / (sum(w) + 1e-8).
+// One thread per output pixel straight from memory (the taps of neighbouring lanes share cache lines).
+template <int K>
+__global__ void __launch_bounds__(256) bilateral_kernel(const float* __restrict__ x, float* __restrict__ out,
+                                                        long long total, int H, int W, PostWeights wt, float inv2sr) {
+  constexpr int P = K / 2;
+  const long long HW = (long long)H * W;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const long long plane = i / HW;
+    const int px = (int)(i - plane * HW);
+    const int y = px / W, xx = px - y * W;
+    const float* src = x + plane * HW;
+    const float c = src[px];
+    float sw = 0.f, sv = 0.f;
+#pragma unroll
+    for (int dy = 0; dy < K; ++dy) {
+      int yy = y + dy - P;
+      yy = yy < 0 ? -yy : (yy >= H ? 2 * (H - 1) - yy : yy);
+#pragma unroll
+      for (int dx = 0; dx < K; ++dx) {
+        int xq = xx + dx - P;
+        xq = xq < 0 ? -xq : (xq >= W ? 2 * (W - 1) - xq : xq);
+        const float p = src[yy * W + xq];
+        const float d = p - c;
+        const float w = wt.w[dy * K + dx] * expf(-(d * d) * inv2sr);
+        sw += w;
+        sv = fmaf(p, w, sv);
+      }
+    }
+    out[i] = sv / (sw + 1e-8f);
+  }
+}
+
+}  // namespace hiseg
+
+using namespace hiseg;
+
+namespace {
+
+struct PostPlan {
+  PostGeom g;
+  unsigned grid, block;
+  size_t lds;
+};
+
+bool post_resident(int H, int W, int force_tiled) { return !force_tiled && (long long)H * W <= kResidentPx; }
+
+// Shape checks and the launch plan shared by the LDS kernels; `halo` is the tiled form's R.
+int post_plan(const char* what, const void* x, const void* out, long long NC, int H, int W, int halo, int force_tiled,
+              PostPlan* p) {
+  HISEG_REQUIRE(NC >= 0 && H >= 0 && W >= 0 && (long long)H * W <= 0x7fffffffll, HISEG_ERR_BAD_SHAPE,
+                "%s: planes %lld H %d W %d", what, NC, H, W);
+  PostGeom& g = p->g;
+  g.H = H;
+  g.W = W;
+  p->grid = 0;
+  if (NC == 0 || H == 0 || W == 0) return HISEG_OK;   // nothing to do (an empty tensor has no address)
+  HISEG_REQUIRE(x && out, HISEG_ERR_BAD_ARG, "%s: null pointer", what);
+  if (post_resident(H, W, force_tiled)) {
+    g.TH = H; g.TW = W; g.tiles_x = 1; g.tiles = 1; g.R = 0;
+    const int px = H * W;
+    p->block = px >= 1024 ? 1024u : (unsigned)((px + 63) / 64 * 64);
+  } else {
+    HISEG_REQUIRE(halo <= kMaxHalo, HISEG_ERR_BAD_ARG,
+                  "%s: the tiled form holds a halo of at most %d pixels, iterations x radius is %d "
+                  "(hiseg_post_max_iterations; split the launch)", what, kMaxHalo, halo);
+    g.TH = g.TW = kPostTile;
+    g.R = halo;
+    g.tiles_x = (W + kPostTile - 1) / kPostTile;
+    g.tiles = g.tiles_x * ((H + kPostTile - 1) / kPostTile);
+    p->block = 256;
+  }
+  const long long blocks = NC * g.tiles;
+  HISEG_REQUIRE(blocks <= 0x7fffffffll, HISEG_ERR_BAD_SHAPE, "%s: %lld workgroups", what, blocks);
+  p->grid = (unsigned)blocks;
+  p->lds = (size_t)(g.TH + 2 * g.R) * (g.TW + 2 * g.R) * 2 * sizeof(float);
+  return HISEG_OK;
+}
+
+// Normalised Gaussian as the outer product of the normalised 1-D kernel (bilateral_filter.py:149-152, 334-345,
+// 438-445), or the unnormalised 2-D spatial kernel of BilateralFilter (45-56).
+void gaussian_weights(int k, float sigma, bool normalised, PostWeights* w) {
+  float g1[kMaxK], sum = 0.f;
+  for (int i = 0; i < k; ++i) {
+    const float c = (float)i - (float)(k - 1) / 2.f;
+    g1[i] = expf(-(c * c) / (2.f * sigma * sigma));
+    sum += g1[i];
+  }
+  for (int y = 0; y < k; ++y)
+    for (int x = 0; x < k; ++x) {
+      if (normalised) {
+        w->w[y * k + x] = (g1[y] / sum) * (g1[x] / sum);
+      } else {
+        const float cy = (float)y - (float)(k - 1) / 2.f, cx = (float)x - (float)(k - 1) / 2.f;
+        w->w[y * k + x] = expf(-(cx * cx + cy * cy) / (2.f * sigma * sigma));
+      }
+    }
+  for (int i = k * k; i < kMaxK * kMaxK; ++i) w->w[i] = 0.f;
+}
+
+bool good_k(int k) { return k >= 3 && k <= kMaxK && (k & 1); }
+
+template <typename Kern, typename... Args>
+void post_launch(Kern kern, const PostPlan& p, hipStream_t s, Args... args) {
+  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kPostLds);
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.block), p.lds, s, args...);
+}
+
+int edge_smooth(const char* what, int mode, const float* x, float* out, long long NC, int H, int W,
+                float threshold, float blur_strength, int iterations, int force_tiled, hiseg_stream_t stream) {
+  HISEG_REQUIRE(iterations >= 1, HISEG_ERR_BAD_ARG, "%s: iterations %d", what, iterations);
+  PostPlan p;
+  const int st = post_plan(what, x, out, NC, H, W, iterations > kMaxHalo ? kMaxHalo + 1 : iterations, force_tiled, &p);
+  if (st != HISEG_OK || p.grid == 0) return st;
+  hipStream_t s = (hipStream_t)stream;
+  if (mode == kEdgeClasses)
+    post_launch(edge_smooth_kernel<kEdgeClasses>, p, s, x, out, p.g, threshold, blur_strength, iterations);
+  else if (mode == kEdgeBinarize)
+    post_launch(edge_smooth_kernel<kEdgeBinarize>, p, s, x, out, p.g, threshold, blur_strength, iterations);
+  else
+    post_launch(edge_smooth_kernel<kEdgePlain>, p, s, x, out, p.g, threshold, blur_strength, iterations);
+  return hiseg_check_launch(what);
+}
+
+}  // namespace
+
+extern "C" int hiseg_post_max_iterations(int H, int W, int radius, int force_tiled) {
+  if (radius < 1 || post_resident(H, W, force_tiled)) return 0x7fffffff;
+  return kMaxHalo / radius;
+}
+
+extern "C" int hiseg_edge_smooth_fwd(const float* x, float* out, long long NC, int H, int W, float threshold,
+                                     float blur_strength, int iterations, int binarize_input, int force_tiled,
+                                     hiseg_stream_t stream) {
+  return edge_smooth("edge_smooth", binarize_input ? kEdgeBinarize : kEdgePlain, x, out, NC, H, W, threshold,
+                     blur_strength, iterations, force_tiled, stream);
+}
+
+extern "C" int hiseg_class_edge_smooth_fwd(const float* scores, float* out, long long B, int H, int W,
+                                           float threshold, float blur_strength, int iterations, int force_tiled,
+                                           hiseg_stream_t stream) {
+  HISEG_REQUIRE(B >= 0 && B <= 0x7fffffffll, HISEG_ERR_BAD_SHAPE, "class_edge_smooth: batch %lld", B);
+  return edge_smooth("class_edge_smooth", kEdgeClasses, scores, out, B * 3, H, W, threshold, blur_strength, iterations,
+                     force_tiled, stream);
+}
+
+extern "C" int hiseg_var_gated_blur_fwd(const float* x, float* out, long long NC, int H, int W, int kernel_size,
+                                        float sigma_spatial, float gain, int clamp_input, int threshold_output,
+                                        float threshold, int iterations, int force_tiled, hiseg_stream_t stream) {
+  HISEG_REQUIRE(good_k(kernel_size), HISEG_ERR_BAD_ARG, "var_gated_blur: kernel_size %d (odd, 3..9)", kernel_size);
+  HISEG_REQUIRE(iterations >= 1 && sigma_spatial > 0.f, HISEG_ERR_BAD_ARG, "var_gated_blur: iterations %d sigma %g",
+                iterations, (double)sigma_spatial);
+  PostPlan p;
+  const long long halo = (long long)iterations * (kernel_size / 2);
+  const int st = post_plan("var_gated_blur", x, out, NC, H, W, halo > kMaxHalo ? kMaxHalo + 1 : (int)halo,
+                           force_tiled, &p);
+  if (st != HISEG_OK || p.grid == 0) return st;
+  PostWeights wt;
+  gaussian_weights(kernel_size, sigma_spatial, true, &wt);
+  hipStream_t s = (hipStream_t)stream;
+#define HISEG_VGB(K)                                                                                          \
+  case K:                                                                                                     \
+    post_launch(var_gated_blur_kernel<K>, p, s, x, out, p.g, wt, gain, clamp_input, threshold_output, threshold, \
+                iterations);                                                                                  \
+    break;
+  switch (kernel_size) { HISEG_VGB(3) HISEG_VGB(5) HISEG_VGB(7) HISEG_VGB(9) }
+#undef HISEG_VGB
+  return hiseg_check_launch("var_gated_blur");
+}
+
+extern "C" int hiseg_morph_bilateral_fwd(const float* x, float* out, long long NC, int H, int W, int kernel_size,
+                                         float sigma, int morph_size, int force_tiled, hiseg_stream_t stream) {
+  HISEG_REQUIRE(good_k(kernel_size), HISEG_ERR_BAD_ARG, "morph_bilateral: kernel_size %d (odd, 3..9)", kernel_size);
+  HISEG_REQUIRE(morph_size >= 1 && morph_size <= kMaxK && (morph_size & 1) && sigma > 0.f, HISEG_ERR_BAD_ARG,
+                "morph_bilateral: morph_size %d (odd, 1..9) sigma %g", morph_size, (double)sigma);
+  PostPlan p;
+  const int st = post_plan("morph_bilateral", x, out, NC, H, W, 4 * (morph_size / 2) + kernel_size / 2, force_tiled,
+                           &p);
+  if (st != HISEG_OK || p.grid == 0) return st;
+  PostWeights wt;
+  gaussian_weights(kernel_size, sigma, true, &wt);
+  hipStream_t s = (hipStream_t)stream;
+#define HISEG_MB(K)                                                                  \
+  case K:                                                                            \
+    post_launch(morph_bilateral_kernel<K>, p, s, x, out, p.g, wt, morph_size / 2);   \
+    break;
+  switch (kernel_size) { HISEG_MB(3) HISEG_MB(5) HISEG_MB(7) HISEG_MB(9) }
+#undef HISEG_MB
+  return hiseg_check_launch("morph_bilateral");
+}
+
+extern "C" int hiseg_bilateral_fwd(const float* x, float* out, long long NC, int H, int W, int kernel_size,
+                                   float sigma_spatial, float sigma_range, hiseg_stream_t stream) {
+  HISEG_REQUIRE(good_k(kernel_size), HISEG_ERR_BAD_ARG, "bilateral: kernel_size %d (odd, 3..9)", kernel_size);
+  HISEG_REQUIRE(sigma_spatial > 0.f && sigma_range > 0.f, HISEG_ERR_BAD_ARG, "bilateral: sigma %g %g",
+                (double)sigma_spatial, (double)sigma_range);
+  HISEG_REQUIRE(NC >= 0 && H >= 0 && W >= 0 && (long long)H * W <= 0x7fffffffll, HISEG_ERR_BAD_SHAPE,
+                "bilateral: planes %lld H %d W %d", NC, H, W);
+  if (NC == 0 || H == 0 || W == 0) return HISEG_OK;
+  HISEG_REQUIRE(x && out, HISEG_ERR_BAD_ARG, "bilateral: null pointer");
+  HISEG_REQUIRE(H > kernel_size / 2 && W > kernel_size / 2, HISEG_ERR_BAD_ARG,
+                "bilateral: reflect padding %d needs H, W > %d (got %d x %d)", kernel_size / 2, kernel_size / 2, H, W);
+  const long long HW = (long long)H * W;
+  HISEG_REQUIRE(NC <= 0x7fffffffffffffffll / HW, HISEG_ERR_BAD_SHAPE, "bilateral: planes %lld", NC);
+  const long long total = NC * HW;
+  PostWeights wt;
+  gaussian_weights(kernel_size, sigma_spatial, false, &wt);
+  const float inv2sr = 1.f / (2.f * sigma_range * sigma_range);
+  const long long blocks = (total + 255) / 256;
+  const dim3 grid((unsigned)(blocks < 65536 * 16 ? blocks : 65536 * 16));
+  hipStream_t s = (hipStream_t)stream;
+#define HISEG_BL(K)                                                                                            \
+  case K:                                                                                                      \
+    hipLaunchKernelGGL(bilateral_kernel<K>, grid, dim3(256), 0, s, x, out, total, H, W, wt, inv2sr);           \
+    break;
+  switch (kernel_size) { HISEG_BL(3) HISEG_BL(5) HISEG_BL(7) HISEG_BL(9) }
+#undef HISEG_BL
+  return hiseg_check_launch("bilateral");
+}

@@ -364,6 +364,14 @@ def _declare(lib):
         "hiseg_pil_resample_h": ([P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P], c_int),
         "hiseg_pil_resample_v": ([P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P], c_int),
         "hiseg_roi_targets": ([P, P, c_int, c_int, c_int, P, P], c_int),
+        # ---- mask post-processing (include/hiseg_post.h)
+        "hiseg_post_max_iterations": ([c_int, c_int, c_int, c_int], c_int),
+        "hiseg_edge_smooth_fwd": ([P, P, c_ll, c_int, c_int, c_float, c_float, c_int, c_int, c_int, P], c_int),
+        "hiseg_class_edge_smooth_fwd": ([P, P, c_ll, c_int, c_int, c_float, c_float, c_int, c_int, P], c_int),
+        "hiseg_var_gated_blur_fwd": ([P, P, c_ll, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_float, c_int,
+                                      c_int, P], c_int),
+        "hiseg_morph_bilateral_fwd": ([P, P, c_ll, c_int, c_int, c_int, c_float, c_int, c_int, P], c_int),
+        "hiseg_bilateral_fwd": ([P, P, c_ll, c_int, c_int, c_int, c_float, c_float, P], c_int),
         "hiseg_optim_blocks": ([], c_int),
         "hiseg_grad_norm_partials": ([P, c_ll, P, P], c_int),
         "hiseg_adamw_step": ([P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_float, c_float, c_float, P,

@@ -520,3 +520,93 @@ def binary_masks(u: torch.Tensor, oc_w: torch.Tensor, oc_b: torch.Tensor) -> tor
     L.check(L.lib().hiseg_binary_masks_fwd(L.HISEG_F32, u.data_ptr(), 1, B, H, W, oc_w.data_ptr(), oc_b.data_ptr(),
                                            out.data_ptr(), L.stream_ptr()), "binary_masks")
     return out
+
+
+# ---- mask post-processing (include/hiseg_post.h): f32 planes [..., H, W], any leading dimensions
+
+
+def _post_planes(x: torch.Tensor, what: str):
+    _require_gpu(x)
+    if x.dim() < 2:
+        raise ValueError(f"{what}: expected [..., H, W] planes, got shape {tuple(x.shape)}")
+    x = x.to(torch.float32).contiguous()
+    H, W = x.shape[-2:]
+    return x, (x.numel() // (H * W) if H * W else 0), H, W
+
+
+def _post_chunks(iterations: int, H: int, W: int, radius: int, force_tiled: bool):
+    """Iterations per launch: one launch in the LDS-resident form, at most a 32-pixel halo per launch in the tiled
+    form (the launches compose to the same bits)."""
+    if iterations < 1:
+        raise ValueError(f"iterations must be >= 1, got {iterations}")
+    cap = L.lib().hiseg_post_max_iterations(H, W, radius, int(force_tiled))
+    out = []
+    while iterations > 0:
+        out.append(min(iterations, cap))
+        iterations -= out[-1]
+    return out
+
+
+def edge_smooth(x: torch.Tensor, threshold: float = 0.5, blur_strength: float = 3.0, iterations: int = 1, *,
+                binarize_input: bool = False, _force_tiled: bool = False) -> torch.Tensor:
+    """BinaryMaskEdgeSmoothing applied `iterations` times to every H x W plane of x; f32 in, f32 0/1 out."""
+    x, NC, H, W = _post_planes(x, "edge_smooth")
+    for n in _post_chunks(iterations, H, W, 1, _force_tiled):
+        out = torch.empty_like(x)
+        L.check(L.lib().hiseg_edge_smooth_fwd(x.data_ptr(), out.data_ptr(), NC, H, W, threshold, blur_strength, n,
+                                              int(binarize_input), int(_force_tiled), L.stream_ptr()), "edge_smooth")
+        x, binarize_input = out, False
+    return x
+
+
+def class_edge_smooth(scores: torch.Tensor, threshold: float = 0.5, blur_strength: float = 3.0, iterations: int = 1,
+                      *, _force_tiled: bool = False) -> torch.Tensor:
+    """[B,3,H,W] scores -> [B,3,H,W]: the masks argmax == c, each smoothed `iterations` times."""
+    if scores.dim() != 4 or scores.shape[1] != 3:
+        raise ValueError(f"class_edge_smooth: expected [B,3,H,W] scores, got shape {tuple(scores.shape)}")
+    x, _, H, W = _post_planes(scores, "class_edge_smooth")
+    chunks = _post_chunks(iterations, H, W, 1, _force_tiled)
+    out = torch.empty_like(x)
+    L.check(L.lib().hiseg_class_edge_smooth_fwd(x.data_ptr(), out.data_ptr(), x.shape[0], H, W, threshold,
+                                                blur_strength, chunks[0], int(_force_tiled), L.stream_ptr()),
+            "class_edge_smooth")
+    rest = iterations - chunks[0]
+    return edge_smooth(out, threshold, blur_strength, rest, _force_tiled=_force_tiled) if rest else out
+
+
+def var_gated_blur(x: torch.Tensor, kernel_size: int, sigma_spatial: float, gain: float, iterations: int, *,
+                   clamp_input: bool = False, threshold: Optional[float] = None,
+                   _force_tiled: bool = False) -> torch.Tensor:
+    """x <- w*f + (1-w)*x, f = G*x, w = exp(-max(G*x^2 - f^2, 0) * gain), `iterations` times; `threshold` set:
+    the result is (x > threshold) as 0/1."""
+    x, NC, H, W = _post_planes(x, "var_gated_blur")
+    chunks = _post_chunks(iterations, H, W, max(kernel_size // 2, 1), _force_tiled)
+    for i, n in enumerate(chunks):
+        last = i == len(chunks) - 1
+        out = torch.empty_like(x)
+        L.check(L.lib().hiseg_var_gated_blur_fwd(
+            x.data_ptr(), out.data_ptr(), NC, H, W, kernel_size, sigma_spatial, gain, int(clamp_input and i == 0),
+            int(last and threshold is not None), threshold if threshold is not None else 0.0, n, int(_force_tiled),
+            L.stream_ptr()), "var_gated_blur")
+        x = out
+    return x
+
+
+def morph_bilateral(x: torch.Tensor, kernel_size: int = 5, sigma: float = 1.0, morph_size: int = 3, *,
+                    _force_tiled: bool = False) -> torch.Tensor:
+    """MorphologicalBilateralFilter on every plane: clamp, open, Gaussian, close, > 0.5."""
+    x, NC, H, W = _post_planes(x, "morph_bilateral")
+    out = torch.empty_like(x)
+    L.check(L.lib().hiseg_morph_bilateral_fwd(x.data_ptr(), out.data_ptr(), NC, H, W, kernel_size, sigma, morph_size,
+                                              int(_force_tiled), L.stream_ptr()), "morph_bilateral")
+    return out
+
+
+def bilateral(x: torch.Tensor, kernel_size: int = 5, sigma_spatial: float = 1.0,
+              sigma_range: float = 0.1) -> torch.Tensor:
+    """The true bilateral filter with reflect padding on every plane."""
+    x, NC, H, W = _post_planes(x, "bilateral")
+    out = torch.empty_like(x)
+    L.check(L.lib().hiseg_bilateral_fwd(x.data_ptr(), out.data_ptr(), NC, H, W, kernel_size, sigma_spatial,
+                                        sigma_range, L.stream_ptr()), "bilateral")
+    return out

@@ -1,0 +1,74 @@
+/*
+ * hiseg_post.h — mask post-processing on the GPU: the clean-up stage the reference runs on the exported
+ * instance / binary masks (src/human_edge_detection/edge_smoothing.py, bilateral_filter.py; exported as separate
+ * graphs by export_edge_smoothing_onnx.py and export_bilateral_filter.py).  Conventions as in hiseg.h.
+ *
+ * Every entry point takes f32 NCHW planes with C folded into N: NC contiguous planes of H x W, x and out distinct
+ * buffers of the same size.  All arithmetic is f32.  NC * H * W == 0 returns HISEG_OK without a launch.
+ *
+ * Kernel forms (csrc/postprocess.hip).  A plane of at most 20480 pixels (two f32 working copies in the 160 KB of
+ * LDS: the 64x48 and 128x96 instance masks) is owned by one workgroup: every iteration and stage runs LDS to LDS,
+ * the plane is read once and written once.  Larger planes (the 480x640 binary masks) take 64x64 tiles with a
+ * halo of iterations x radius pixels (summed radii for the morphological chain), at most 32; each tile recomputes
+ * its halo, and pixels outside the image are re-padded as the reference pads them at every iteration.  Both forms
+ * give the same bits, and N iterations in one launch the same bits as N launches.  force_tiled != 0 takes the
+ * tiled form at any size (tests).
+ */
+#ifndef HISEG_POST_H_
+#define HISEG_POST_H_
+
+#include "hiseg.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Host function (no GPU): the largest `iterations` one launch accepts for a stencil of this radius on H x W
+ * planes -- 32 / radius in the tiled form, INT_MAX in the LDS-resident form.  A caller with more splits the
+ * launches (the results are the same bits). */
+int hiseg_post_max_iterations(int H, int W, int radius, int force_tiled);
+
+/* BinaryMaskEdgeSmoothing.forward (edge_smoothing.py:34-90) applied `iterations` >= 1 times: 3x3 Laplacian,
+ * e = sigmoid(|lap| * blur_strength), 3x3 (1,2,1)/16 Gaussian b, m*(1-e) + b*e, > threshold -> 1.0 / 0.0.  Both
+ * convolutions zero padded.  The sigmoid and the blend are evaluated in f32 in the reference's operation order
+ * (1/(1+exp(-x)), then m*(1-e) + b*e, no fused multiply-add): on a binary mask the reference's decision at a
+ * blend of exactly 0.5 (sigmoid(18) rounds to 1.0f) is reproduced bit for bit.  binarize_input != 0 smooths the
+ * mask (x > 0.5) instead of x (the probability-map path of MultiClassEdgeSmoothing, edge_smoothing.py:144). */
+int hiseg_edge_smooth_fwd(const float* x, float* out, long long NC, int H, int W, float threshold,
+                          float blur_strength, int iterations, int binarize_input, int force_tiled,
+                          hiseg_stream_t stream);
+
+/* MultiClassEdgeSmoothing.smooth_predictions, 3-class path (edge_smoothing.py:127-150): scores [B][3][H][W] ->
+ * out [B][3][H][W], plane c = the mask (argmax over the 3 scores == c) smoothed `iterations` times as above.  On
+ * ties the first maximum wins (torch.argmax); the one-hot planes are formed while loading and never reach
+ * memory.  NaN scores are out of scope: a NaN is never the maximum here, while torch.argmax picks it. */
+int hiseg_class_edge_smooth_fwd(const float* scores, float* out, long long B, int H, int W, float threshold,
+                                float blur_strength, int iterations, int force_tiled, hiseg_stream_t stream);
+
+/* BinaryMaskBilateralFilter.forward (bilateral_filter.py:349-406) and FastBilateralFilter.forward (158-216) in
+ * one kernel.  Per iteration f = G*x, v = max(G*x^2 - f^2, 0), w = exp(-v * gain), x <- w*f + (1-w)*x, with G the
+ * normalised kernel_size x kernel_size Gaussian of sigma_spatial (kernel_size odd, 3..9), zero padded.
+ * gain: 10 for the binary-mask filter, 1 / (2 sigma_range^2) for the fast filter.  clamp_input != 0 clamps x to
+ * [0, 1] first; threshold_output != 0 writes (x > threshold) as 1.0 / 0.0 instead of x. */
+int hiseg_var_gated_blur_fwd(const float* x, float* out, long long NC, int H, int W, int kernel_size,
+                             float sigma_spatial, float gain, int clamp_input, int threshold_output,
+                             float threshold, int iterations, int force_tiled, hiseg_stream_t stream);
+
+/* MorphologicalBilateralFilter.forward (bilateral_filter.py:473-501): clamp to [0, 1], open (min then max over
+ * morph_size x morph_size), kernel_size x kernel_size normalised Gaussian of sigma (zero padded), close (max
+ * then min), > 0.5 -> 1.0 / 0.0.  max_pool2d pads with -inf: neither min nor max sees the padding.  kernel_size
+ * odd 3..9, morph_size odd 1..9. */
+int hiseg_morph_bilateral_fwd(const float* x, float* out, long long NC, int H, int W, int kernel_size, float sigma,
+                              int morph_size, int force_tiled, hiseg_stream_t stream);
+
+/* BilateralFilter.forward (bilateral_filter.py:60-113): the true bilateral filter with reflect padding, weight
+ * exp(-(dx^2+dy^2) / (2 sigma_spatial^2)) * exp(-(p - c)^2 / (2 sigma_range^2)), normalised by (sum + 1e-8).
+ * H, W > kernel_size / 2 as F.pad(mode='reflect') requires, else HISEG_ERR_BAD_ARG. */
+int hiseg_bilateral_fwd(const float* x, float* out, long long NC, int H, int W, int kernel_size,
+                        float sigma_spatial, float sigma_range, hiseg_stream_t stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif

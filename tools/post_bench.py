@@ -1,0 +1,168 @@
+"""Mask post-processing micro-benchmark (developer tool, GPU): the hiseg kernels of include/hiseg_post.h against the
+same formulas composed from torch-ROCm ops, at the C2 export shapes -- 256 x 1 x 128 x 96 instance masks (LDS-resident
+form) and 32 x 1 x 480 x 640 binary masks (tiled form).
+
+Per filter (class defaults) and shape: us per call from HIP events (WARMUP untimed calls, then the median of REPEATS
+windows of CALLS calls each), for hiseg and for the torch composition, and the hiseg kernel's fraction of the HBM peak
+at the algorithmic 8 bytes per pixel (one f32 read, one f32 write; 8.0 TB/s, MI355X spec).  The multi-class front end
+reads three score planes per pixel and writes three masks: 24 bytes per pixel of the [B,3,H,W] input.  The windows
+include launch overhead and any dtype / layout plumbing of the Python wrappers: it is a call time, not a kernel time.
+
+The torch compositions below restate the formulas of hiseg_post.h with F.conv2d / F.max_pool2d (zero padding, -inf
+padding for the pools, separable convolutions for the fast filter), which is how a user without these kernels
+would run them on the GPU.  BilateralFilter has no torch composition short of an unfold over k*k taps: that unfold
+is what is timed.  Outputs are compared once per filter and shape (fraction of differing pixels for thresholded
+outputs, max |diff| for soft ones) so that the two columns time the same function.
+
+Prints one JSON object; --markdown adds the table for DESIGN.md.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "human-instance-segmentation_amd"))
+import hiseg  # noqa: E402
+
+HBM_PEAK = 8.0e12   # bytes / s
+WARMUP, REPEATS, CALLS = 10, 7, 20
+SHAPES = {"roi 256x1x128x96": (256, 1, 128, 96), "full 32x1x480x640": (32, 1, 480, 640)}
+
+
+def gauss1d(k, sigma, dev):
+    c = torch.arange(k, dtype=torch.float32, device=dev) - (k - 1) / 2
+    g = torch.exp(-c ** 2 / (2 * sigma ** 2))
+    return g / g.sum()
+
+
+def t_edge(x, threshold=0.5, blur=3.0):
+    lap_k = torch.tensor([[-1., -1, -1], [-1, 8, -1], [-1, -1, -1]], device=x.device)[None, None]
+    g_k = torch.tensor([[1., 2, 1], [2, 4, 2], [1, 2, 1]], device=x.device)[None, None] / 16
+    e = torch.sigmoid(F.conv2d(x, lap_k, padding=1).abs() * blur)
+    return (x * (1 - e) + F.conv2d(x, g_k, padding=1) * e > threshold).float()
+
+
+def t_classes(s, iterations=1):
+    am = s.argmax(dim=1)
+    out = []
+    for c in range(3):
+        m = (am == c).float().unsqueeze(1)
+        for _ in range(iterations):
+            m = t_edge(m)
+        out.append(m[:, 0])
+    return torch.stack(out, dim=1)
+
+
+def t_var_gated(x, k, sigma, gain, iterations, clamp, threshold, separable):
+    g = gauss1d(k, sigma, x.device)
+    g2 = (g[:, None] * g[None, :])[None, None]
+    p = k // 2
+
+    def blur(t):
+        if separable:
+            return F.conv2d(F.conv2d(t, g.view(1, 1, 1, k), padding=(0, p)), g.view(1, 1, k, 1), padding=(p, 0))
+        return F.conv2d(t, g2, padding=p)
+    if clamp:
+        x = x.clamp(0, 1)
+    for _ in range(iterations):
+        f = blur(x)
+        w = torch.exp(-(blur(x * x) - f * f).clamp(min=0) * gain)
+        x = w * f + (1 - w) * x
+    return (x > threshold).float() if threshold is not None else x
+
+
+def t_morph(x, k=5, sigma=1.0, m=3):
+    g = gauss1d(k, sigma, x.device)
+
+    def pool(t):
+        return F.max_pool2d(t, m, stride=1, padding=m // 2)
+    x = pool(-pool(-x.clamp(0, 1)))
+    x = F.conv2d(x, (g[:, None] * g[None, :])[None, None], padding=k // 2)
+    return (-pool(-pool(x)) > 0.5).float()
+
+
+def t_bilateral(x, k=5, sigma_s=1.0, sigma_r=0.1):
+    B, C, H, W = x.shape
+    c = torch.arange(k, dtype=torch.float32, device=x.device) - (k - 1) / 2
+    sp = torch.exp(-(c[:, None] ** 2 + c[None, :] ** 2) / (2 * sigma_s ** 2)).reshape(1, k * k, 1)
+    out = []
+    for b in range(B):   # one image at a time: the unfold holds k*k copies of the plane
+        xb = x[b:b + 1].reshape(C, 1, H, W)
+        patches = F.unfold(F.pad(xb, [k // 2] * 4, mode="reflect"), k)          # [C, k*k, H*W]
+        w = sp * torch.exp(-(patches - xb.reshape(C, 1, H * W)) ** 2 / (2 * sigma_r ** 2))
+        out.append(((patches * w).sum(1) / (w.sum(1) + 1e-8)).reshape(1, C, H, W))
+    return torch.cat(out)
+
+
+def time_us(fn):
+    for _ in range(WARMUP):
+        fn()
+    torch.cuda.synchronize()
+    windows = []
+    for _ in range(REPEATS):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(CALLS):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        windows.append(e0.elapsed_time(e1) / CALLS * 1e3)
+    return statistics.median(windows), min(windows), max(windows)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--markdown", action="store_true")
+    args = ap.parse_args()
+    dev = torch.device("cuda")
+    gen = torch.Generator(device=dev).manual_seed(11)
+    rows = []
+    for sname, shape in SHAPES.items():
+        B, _, H, W = shape
+        yy, xx = torch.meshgrid(torch.linspace(-1, 1, H, device=dev), torch.linspace(-1, 1, W, device=dev), indexing="ij")
+        field = 1 - ((yy / 0.6) ** 2 + (xx / 0.5) ** 2)
+        binary = ((field > 0) ^ (torch.rand(shape, device=dev, generator=gen) < 0.08)).float()
+        soft = torch.sigmoid(4 * field) + 0.1 * torch.randn(shape, device=dev, generator=gen)
+        scores = torch.randn(B, 3, H, W, device=dev, generator=gen)
+        mods = {n: getattr(hiseg, n)().to(dev) for n in ("BinaryMaskEdgeSmoothing", "BinaryMaskBilateralFilter",
+                                                         "FastBilateralFilter", "MorphologicalBilateralFilter",
+                                                         "BilateralFilter")}
+        mc = hiseg.MultiClassEdgeSmoothing(device="cuda")
+        cases = (
+            ("edge_smooth", binary, mods["BinaryMaskEdgeSmoothing"], t_edge, 8),
+            ("class_edge_smooth", scores, mc.smooth_predictions, t_classes, 24),
+            ("var_gated_blur (BinaryMaskBilateralFilter k7 x2)", binary, mods["BinaryMaskBilateralFilter"],
+             lambda t: t_var_gated(t, 7, 1.5, 10.0, 2, True, 0.5, False), 8),
+            ("var_gated_blur (FastBilateralFilter k5 x2)", soft, mods["FastBilateralFilter"],
+             lambda t: t_var_gated(t, 5, 1.0, 1 / (2 * 0.1 ** 2), 2, False, None, True), 8),
+            ("morph_bilateral (k5, morph 3)", binary, mods["MorphologicalBilateralFilter"], t_morph, 8),
+            ("bilateral (k5)", soft, mods["BilateralFilter"], t_bilateral, 8),
+        )
+        for name, x, ours, theirs, bpp in cases:
+            with torch.no_grad():
+                a, b = ours(x), theirs(x)
+                soft_out = name.startswith("var_gated_blur (Fast") or name.startswith("bilateral")
+                diff = float((a - b).abs().max()) if soft_out else float((a != b).float().mean())
+                us, lo, hi = time_us(lambda: ours(x))
+                tus, tlo, thi = time_us(lambda: theirs(x))
+            px = B * H * W
+            rows.append({"filter": name, "shape": sname, "hiseg_us": round(us, 1), "hiseg_us_min_max": [round(lo, 1), round(hi, 1)],
+                         "torch_us": round(tus, 1), "torch_us_min_max": [round(tlo, 1), round(thi, 1)],
+                         "speedup": round(tus / us, 2), "bytes_per_pixel": bpp,
+                         "hbm_peak_fraction": round(px * bpp / (us * 1e-6) / HBM_PEAK, 4),
+                         ("max_abs_diff" if soft_out else "pixels_differing"): diff})
+    print(json.dumps({"hbm_peak_Bps": HBM_PEAK, "warmup": WARMUP, "repeats": REPEATS, "calls": CALLS, "rows": rows}))
+    if args.markdown:
+        print("| filter | shape | hiseg us | torch composition us | x | HBM peak fraction |")
+        print("|---|---|---|---|---|---|")
+        for r in rows:
+            print(f"| {r['filter']} | {r['shape']} | {r['hiseg_us']} | {r['torch_us']} | {r['speedup']} | "
+                  f"{100 * r['hbm_peak_fraction']:.1f} % |")
+
+
+if __name__ == "__main__":
+    main()
