@@ -6,7 +6,7 @@ on a full-image EfficientNet-UNet).  Module tree and state_dict keys follow the 
 every forward runs on libhiseg (hand-written gfx950 HIP kernels, C ABI in include/hiseg.h).
 """
 from .layers import (  # noqa: F401
-    ChannelAttentionModule, ContourDetectionBranch, DistanceTransformDecoder, EnhancedUNet,
+    BoundaryRefinementModule, ChannelAttentionModule, ContourDetectionBranch, DistanceTransformDecoder, EnhancedUNet,
     ExtendedHierarchicalSegmentationHeadUNetV2, LayerNorm2d, RefinedHierarchicalSegmentationHead, ResidualBlock,
     SpatialAttentionModule)
 from .effunet import EfficientNetUnet  # noqa: F401
@@ -15,7 +15,7 @@ from .model import (  # noqa: F401
     PreTrainedPeopleSegmentationUNetWrapper, RGBHierarchicalExportWrapper, StreamPipelinedExport,
     create_rgb_hierarchical_model)
 
-from .losses import RefinedHierarchicalLoss  # noqa: F401,E402
+from .losses import RefinedHierarchicalLoss, active_contour_term  # noqa: F401,E402
 from .optim import FusedAdamW, cosine_lr  # noqa: F401,E402
 from .graphs import GraphedStep, GraphedBranchStep  # noqa: F401,E402
 from .checkpoint import resume_from_checkpoint, save_checkpoint  # noqa: F401,E402

@@ -372,6 +372,17 @@ def _declare(lib):
                                       c_int, P], c_int),
         "hiseg_morph_bilateral_fwd": ([P, P, c_ll, c_int, c_int, c_int, c_float, c_int, c_int, P], c_int),
         "hiseg_bilateral_fwd": ([P, P, c_ll, c_int, c_int, c_int, c_float, c_float, P], c_int),
+        # ---- boundary refinement stage and active-contour loss (include/hiseg_refine.h)
+        "hiseg_edge_map_ws": ([c_int, c_int, c_int], c_ll),
+        "hiseg_edge_map_fwd": ([P, c_int, c_int, c_int, P, P, P, P, c_int, c_int, P, P], c_int),
+        "hiseg_boundary_blend_fwd": ([P, P, c_int, P, P, P, c_int, c_int, c_int, P, P, P], c_int),
+        "hiseg_boundary_refine_fused": ([P, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P, P], c_int),
+        "hiseg_boundary_bwd_ws": ([c_int, c_int, c_int], c_ll),
+        "hiseg_boundary_blend_bwd": ([P, P, c_int, P, P, P, c_int, c_int, c_int, P, c_int, P, P, P], c_int),
+        "hiseg_edge_map_bwd": ([P, P, c_int, c_int, P, P, P, c_int, c_int, c_int, P, P, P], c_int),
+        "hiseg_active_contour_ws": ([c_int, c_int, c_int], c_ll),
+        "hiseg_active_contour_fwd": ([P, c_int, c_int, c_int, P, P, P], c_int),
+        "hiseg_active_contour_bwd": ([P, c_int, c_int, c_int, P, P, P, P], c_int),
         "hiseg_optim_blocks": ([], c_int),
         "hiseg_grad_norm_partials": ([P, c_ll, P, P], c_int),
         "hiseg_adamw_step": ([P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_float, c_float, c_float, P,

@@ -273,6 +273,8 @@ def hier_head(E: Ctx, head: nn.Module, feat: Act, aux: str) -> Tuple[torch.Tenso
         low.t, low.N, low.H, low.W, t, E.f32(up[0].weight), ut_s, ut_h, act_code(up[2]),
         E.f32(up[3].weight, (2, up[3].in_channels)), E.f32(up[3].bias),
         E.f32(last.weight, (2, last.in_channels)), E.f32(last.bias), want, per_sample=per_sample)
+    if head.use_boundary_refinement:   # refines the returned masks only; the aux tensors stay (refinement.py:767-769)
+        logits = boundary_refine(E, head.boundary_refiner, logits)
     auxd: Dict[str, torch.Tensor] = {}
     if not want:
         return logits, auxd
@@ -303,6 +305,44 @@ def hier_head(E: Ctx, head: nn.Module, feat: Act, aux: str) -> Tuple[torch.Tenso
         auxd["distance_mask"] = _resize(dmask, mh, mw, lib)
         auxd["distance_map"] = _resize(dmap, mh, mw, lib)
     return logits, auxd
+
+
+def refine_fused_eligible(mod: nn.Module, dtype: torch.dtype) -> bool:
+    """Whether the fused inference kernel of include/hiseg_refine.h covers this module: bf16 compute dtype, eval
+    mode, both norms BatchNorm (folded), both activations ReLU, 3 -> 32 -> 32 -> 3 channels with biases."""
+    import os
+    ec = mod.edge_conv
+    return (dtype == torch.bfloat16 and not mod.training and os.environ.get("HISEG_REFINE_FUSED", "1") != "0"
+            and isinstance(ec[1], nn.BatchNorm2d) and isinstance(ec[4], nn.BatchNorm2d)
+            and isinstance(ec[2], nn.ReLU) and isinstance(ec[5], nn.ReLU)
+            and tuple(ec[0].weight.shape) == (32, 3, 3, 3) and tuple(ec[3].weight.shape) == (32, 32, 3, 3)
+            and tuple(ec[6].weight.shape) == (3, 32, 1, 1) and ec[6].bias is not None)
+
+
+def boundary_refine(E: Ctx, mod: nn.Module, logits: torch.Tensor, want_edges: bool = False):
+    """BoundaryRefinementModule.forward (refinement.py:131-149), eval mode.  The common case -- bf16 compute dtype,
+    both norms BatchNorm, ReLU, 32 edge channels -- is the edge pass plus ONE fused kernel (refine_fused_eligible;
+    HISEG_REFINE_FUSED=0 turns it off for A/B timing).  Anything else: the edge pass also writes the channel-last
+    copy of the logits the convs read; conv + norm + act launches as everywhere (cna), the last 1x1 into an f32
+    buffer; one blend pass.  ``want_edges``: also return the normalised edge map [N,1,H,W] (conv chain only)."""
+    if mod.training:
+        raise NotImplementedError("hiseg executes the inference (eval-mode) forward; call .eval()")
+    ec = mod.edge_conv
+    if not want_edges and refine_fused_eligible(mod, E.dtype):
+        em = ops.edge_map(logits)
+        s1, t1 = E.affine(("refine1", id(ec[0])), 32, ec[0].bias, ec[1])
+        s2, t2 = E.affine(("refine2", id(ec[3])), 32, ec[3].bias, ec[4])
+        w2f = E._get(("refine_w2", id(ec[3])), lambda: ops.pack_refine_conv2(ec[3].weight, E.device),
+                     (ec[3].weight,))
+        return ops.boundary_refine_fused(em, E.f32(mod.blend_weight, (1,)), E.f32(ec[0].weight, (32, 27)), s1, t1,
+                                         w2f, s2, t2, E.f32(ec[6].weight, (3, 32)), E.f32(ec[6].bias))
+    em = ops.edge_map(logits, cl_dtype=E.dtype)
+    h = cna(E, ec[0], ec[1], act_code(ec[2]), em.x_cl)
+    h = cna(E, ec[3], ec[4], act_code(ec[5]), h)
+    R = Act.new(h.N, h.H, h.W, 3, torch.float32, E.device)
+    ops.conv2d(E.conv(ec[6]), h, out=R)
+    out, edges = ops.boundary_blend(em, R, E.f32(mod.blend_weight, (1,)), want_edges)
+    return (out, edges) if want_edges else out
 
 
 def _resize(x: torch.Tensor, H: int, W: int, lib) -> torch.Tensor:
@@ -547,6 +587,12 @@ def enhanced_unet_nchw(u: nn.Module, x: torch.Tensor) -> torch.Tensor:
     E = Ctx(u, _root_dtype(u), x.device)
     low, _ = enhanced_unet(E, u, Act.from_nchw(x, E.dtype))
     return low.to_nchw()
+
+
+def boundary_refine_nchw(mod: nn.Module, x: torch.Tensor, want_edges: bool = False):
+    _check_input(x, "BoundaryRefinementModule")
+    E = Ctx(mod, _root_dtype(mod), x.device)
+    return boundary_refine(E, mod, x, want_edges)
 
 
 def head_nchw(head: nn.Module, x: torch.Tensor):

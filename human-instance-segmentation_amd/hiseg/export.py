@@ -276,7 +276,16 @@ def rgb_out_templates(model: torch.nn.Module, aux: str) -> List[Tuple[str, list]
     return outs
 
 
+def refuse_boundary_refiner(model: torch.nn.Module) -> None:
+    if getattr(model.segmentation_head, "use_boundary_refinement", False):
+        raise NotImplementedError(
+            "traced / ONNX export of a model with a boundary refiner (use_boundary_refinement=True) is not supported: "
+            "the stage normalises its edge map by the batch-global min and max and branches on their difference, "
+            "which the lowering does not express; export the masks with the eager path (export_forward)")
+
+
 def _head_spec(model: torch.nn.Module, aux: str) -> str:
+    refuse_boundary_refiner(model)
     ma, mr = model.roi_align_mask, model.roi_align_rgb
     scales = [float(ma.spatial_scale_h), float(ma.spatial_scale_w)]
     if [float(mr.spatial_scale_h), float(mr.spatial_scale_w)] != scales or not (ma.aligned and mr.aligned):

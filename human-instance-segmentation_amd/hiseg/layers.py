@@ -196,6 +196,39 @@ class DistanceTransformDecoder(nn.Module):
         self.threshold = nn.Parameter(torch.tensor(0.3))
 
 
+class BoundaryRefinementModule(nn.Module):
+    """x + blend_weight * edge_conv(x) * edges(x) -- advanced/hierarchical_segmentation_refinement.py:58-149.
+
+    The edge map is normalised by the min and max over the whole batch (:122-128).  Eval-mode forwards run through
+    :func:`hiseg.engine.boundary_refine`, train-mode forwards (with gradients for the input and every parameter)
+    through :func:`hiseg.train_engine.boundary_refine_module_train`."""
+
+    def __init__(self, in_channels: int = 3, edge_channels: int = 32, normalization_type: str = "layernorm2d",
+                 normalization_groups: int = 8, activation_function: str = "relu", activation_beta: float = 1.0):
+        super().__init__()
+        if in_channels != 3:
+            raise NotImplementedError("the hiseg boundary refinement kernels are built for the 3-class mask")
+        g = min(normalization_groups, edge_channels)
+        self.edge_conv = nn.Sequential(
+            nn.Conv2d(in_channels, edge_channels, 3, padding=1),
+            make_norm(normalization_type, edge_channels, g), make_act(activation_function, activation_beta),
+            nn.Conv2d(edge_channels, edge_channels, 3, padding=1),
+            make_norm(normalization_type, edge_channels, g), make_act(activation_function, activation_beta),
+            nn.Conv2d(edge_channels, in_channels, 1))
+        self.blend_weight = nn.Parameter(torch.tensor(0.01))
+        for m in self.edge_conv.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.xavier_uniform_(m.weight, gain=0.1)
+                if m.bias is not None:
+                    nn.init.zeros_(m.bias)
+
+    def forward(self, mask_logits: torch.Tensor) -> torch.Tensor:
+        if self.training:
+            from . import train_engine
+            return train_engine.boundary_refine_module_train(self, mask_logits)
+        return _engine().boundary_refine_nchw(self, mask_logits)
+
+
 def _hw(size: Union[int, Tuple[int, int]]) -> Tuple[int, int]:
     if isinstance(size, (tuple, list)):
         return int(size[0]), int(size[1])
@@ -259,10 +292,10 @@ class RefinedHierarchicalSegmentationHead(nn.Module):
                  normalization_groups: int = 8, activation_function: str = "relu", activation_beta: float = 1.0,
                  hierarchical_base_channels: int = 96, hierarchical_depth: int = 3):
         super().__init__()
-        if use_boundary_refinement or use_progressive_upsampling or use_subpixel_conv:
+        if use_progressive_upsampling or use_subpixel_conv:
             raise NotImplementedError(
-                "boundary refinement / progressive upsampling / sub-pixel decoders are not used by the RGB "
-                "hierarchical configs and are outside the hiseg hot path (SURVEY.md §8)")
+                "progressive upsampling / sub-pixel decoders are not used by the RGB hierarchical configs and are "
+                "outside the hiseg hot path (SURVEY.md §8)")
         self.base_head = ExtendedHierarchicalSegmentationHeadUNetV2(
             in_channels, mid_channels, num_classes, mask_size, use_attention_module=use_attention_module,
             normalization_type=normalization_type, normalization_groups=normalization_groups,
@@ -271,13 +304,16 @@ class RefinedHierarchicalSegmentationHead(nn.Module):
         self.mask_size = mask_size
         self.mask_height, self.mask_width = _hw(mask_size)
         self.num_classes = num_classes
-        self.use_boundary_refinement = False
+        self.use_boundary_refinement = bool(use_boundary_refinement)
         self.use_progressive_upsampling = False
         self.use_subpixel_conv = False
         self.use_contour_detection = use_contour_detection
         self.use_distance_transform = use_distance_transform
         args = dict(norm=normalization_type, groups=normalization_groups, act=activation_function,
                     beta=activation_beta)
+        if use_boundary_refinement:   # registered before the aux branches, as the reference does (:685-693)
+            self.boundary_refiner = BoundaryRefinementModule(
+                num_classes, 32, normalization_type, normalization_groups, activation_function, activation_beta)
         if use_contour_detection:
             self.contour_branch = ContourDetectionBranch(mid_channels, 64, **args)
         if use_distance_transform:

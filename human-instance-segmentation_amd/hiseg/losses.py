@@ -5,7 +5,7 @@ Same constructor, same call ``loss_fn(pred, target, aux_outputs) -> (total, loss
 loss-dict keys as the reference.  The forward (targets rasterisation, dynamic class weights with their EMA,
 every loss term, clamps) and the backward run as HIP kernels (include/hiseg_loss.h); the EMA state lives on
 the device, so a step performs no host synchronisation.  ``loss_dict`` values are materialised lazily: the
-first access copies the 15 device scalars to the host once (the reference calls ``.item()`` per term).
+first access copies the device scalars to the host once (the reference calls ``.item()`` per term).
 """
 from __future__ import annotations
 
@@ -51,6 +51,8 @@ class LazyLossDict(Mapping):
                     v[k] = host[7]
                 elif k == "distance_transform":
                     v[k] = host[8]
+            if "active_contour" in self._keys:   # appended after the library's outputs by the loss module
+                v["active_contour"] = host[16]
             v.update(self._extra)
             self._vals = v
         return self._vals
@@ -116,6 +118,40 @@ class _LossFunction(torch.autograd.Function):
         return None, dp, db, dt, dc, dd, None
 
 
+class _ActiveContourFunction(torch.autograd.Function):
+    """min(active_contour_loss(softmax(pred)), 10) (refinement.py:347-386, :920-925) as its own autograd node."""
+
+    @staticmethod
+    def forward(ctx, pred):
+        lib = L.lib()
+        N, _, H, W = pred.shape
+        ws = torch.empty(int(lib.hiseg_active_contour_ws(N, H, W)), dtype=torch.float32, device=pred.device)
+        out = torch.empty(2, dtype=torch.float32, device=pred.device)
+        L.check(lib.hiseg_active_contour_fwd(pred.data_ptr(), N, H, W, ws.data_ptr(), out.data_ptr(), L.stream_ptr()),
+                "active_contour_fwd")
+        ctx.save_for_backward(pred, ws)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, ws = ctx.saved_tensors
+        N, _, H, W = pred.shape
+        dp = torch.empty_like(pred)
+        gs = g.contiguous().float()
+        L.check(L.lib().hiseg_active_contour_bwd(pred.data_ptr(), N, H, W, ws.data_ptr(), gs.data_ptr(), dp.data_ptr(),
+                                                 L.stream_ptr()), "active_contour_bwd")
+        return dp
+
+
+def active_contour_term(pred: torch.Tensor) -> torch.Tensor:
+    """The clamped active-contour term of RefinedHierarchicalLoss on logits [N,3,H,W] (GPU only)."""
+    if not pred.is_cuda:
+        raise RuntimeError("hiseg active_contour_term runs on the GPU only (got a CPU tensor)")
+    if pred.dim() != 4 or pred.shape[1] != 3:
+        raise ValueError(f"active_contour_term: expected [N,3,H,W] logits, got shape {tuple(pred.shape)}")
+    return _ActiveContourFunction.apply(pred.float().contiguous())
+
+
 class RefinedHierarchicalLoss(nn.Module):
     """Hierarchical loss with refinement terms (refinement.py:807-984); arguments as the reference."""
 
@@ -127,8 +163,8 @@ class RefinedHierarchicalLoss(nn.Module):
                  use_contour_detection: bool = False, use_distance_transform: bool = False,
                  base_mask_size: Tuple[int, int] = (64, 48), auto_adjust_contour_weight: bool = True):
         super().__init__()
-        if use_active_contour_loss:
-            raise NotImplementedError("active_contour_loss is not used by the measured configs (SURVEY.md §8a L1)")
+        self.use_active_contour_loss = use_active_contour_loss
+        self.active_contour_weight = active_contour_weight
         self.bg_weight, self.fg_weight, self.target_weight = bg_weight, fg_weight, target_weight
         self.consistency_weight, self.use_dynamic_weights = consistency_weight, use_dynamic_weights
         self.dice_weight, self.ce_weight = dice_weight, ce_weight
@@ -184,6 +220,11 @@ class RefinedHierarchicalLoss(nn.Module):
                                          f32(aux["target_nontarget_logits"]), f32(cont), f32(dist),
                                          target.to(device=pred.device, dtype=torch.int64).contiguous())
         keys = []
+        if self.use_active_contour_loss:   # refinement.py:920-927; its scalar joins the one lazy host copy
+            ac = active_contour_term(pred)
+            total = total + self.active_contour_weight * ac
+            out = torch.cat([out, ac.detach().view(1)])
+            keys.append("active_contour")
         if self.use_boundary_aware_loss:
             keys.append("boundary_aware")
         if adj is not None:

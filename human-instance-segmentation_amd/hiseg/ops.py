@@ -610,3 +610,77 @@ def bilateral(x: torch.Tensor, kernel_size: int = 5, sigma_spatial: float = 1.0,
     L.check(L.lib().hiseg_bilateral_fwd(x.data_ptr(), out.data_ptr(), NC, H, W, kernel_size, sigma_spatial,
                                         sigma_range, L.stream_ptr()), "bilateral")
     return out
+
+
+# ---- boundary refinement stage (include/hiseg_refine.h): f32 NCHW logits [N,3,H,W]
+
+
+def _refine_logits(x: torch.Tensor, what: str):
+    _require_gpu(x)
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"{what}: expected [N,3,H,W] logits, got shape {tuple(x.shape)}")
+    x = x.to(torch.float32).contiguous()
+    N, _, H, W = x.shape
+    return x, N, H, W
+
+
+@dataclass
+class EdgeMap:
+    """What hiseg_edge_map_fwd leaves for the blend and the backward."""
+    x: torch.Tensor                 # the logits [N,3,H,W] f32
+    e_raw: torch.Tensor             # [N,H,W]
+    mnmx: torch.Tensor              # [2], device
+    x_cl: Optional[Act]             # channel-last copy of x in the compute dtype
+    probs: Optional[torch.Tensor]   # softmax(x, 1), kept for the backward
+
+
+def edge_map(x: torch.Tensor, cl_dtype: Optional[torch.dtype] = None, want_probs: bool = False) -> EdgeMap:
+    """detect_edges up to the raw edge strength and its batch-global min / max (refinement.py:98-123)."""
+    x, N, H, W = _refine_logits(x, "edge_map")
+    lib, dev = L.lib(), x.device
+    e = torch.empty(N, H, W, dtype=torch.float32, device=dev)
+    mnmx = torch.empty(2, dtype=torch.float32, device=dev)
+    ws = torch.empty(int(lib.hiseg_edge_map_ws(N, H, W)), dtype=torch.float32, device=dev)
+    probs = torch.empty_like(x) if want_probs else None
+    cl = Act.new(N, H, W, 3, cl_dtype, dev, zero=False) if cl_dtype is not None else None
+    L.check(lib.hiseg_edge_map_fwd(x.data_ptr(), N, H, W, e.data_ptr(), mnmx.data_ptr(), _ptr(probs),
+                                   cl.ptr() if cl is not None else None,
+                                   hdtype(cl_dtype) if cl is not None else 0, cl.cstride if cl is not None else 0,
+                                   ws.data_ptr(), L.stream_ptr()), "edge_map_fwd")
+    return EdgeMap(x, e, mnmx, cl, probs)
+
+
+def boundary_blend(em: EdgeMap, R: Act, blend: torch.Tensor, want_edges: bool = False):
+    """x + blend * R * E (refinement.py:124-147); R: f32 channel-last [N,H,W,3(+pad)], blend: f32 device scalar.
+    Returns (out, E or None)."""
+    N, _, H, W = em.x.shape
+    assert R.dtype == torch.float32 and R.coff == 0 and (R.N, R.H, R.W, R.C) == (N, H, W, 3)
+    out = torch.empty_like(em.x)
+    E = torch.empty(N, 1, H, W, dtype=torch.float32, device=em.x.device) if want_edges else None
+    L.check(L.lib().hiseg_boundary_blend_fwd(em.x.data_ptr(), R.ptr(), R.cstride, em.e_raw.data_ptr(),
+                                             em.mnmx.data_ptr(), blend.data_ptr(), N, H, W, out.data_ptr(), _ptr(E),
+                                             L.stream_ptr()), "boundary_blend_fwd")
+    return out, E
+
+
+def pack_refine_conv2(w2: torch.Tensor, device) -> torch.Tensor:
+    """conv2's weights [32,32,3,3] as bf16 MFMA A-operand fragments [tap][tile][lane][8] (include/hiseg_refine.h):
+    element j of lane l of tile t is w2[16 t + (l & 15)][8 (l >> 4) + j][ky][kx]."""
+    assert tuple(w2.shape) == (32, 32, 3, 3)
+    w = w2.detach().to(device=device, dtype=torch.float32).permute(2, 3, 0, 1).reshape(9, 2, 16, 4, 8)
+    return w.permute(0, 1, 3, 2, 4).contiguous().to(torch.bfloat16).reshape(9, 2, 64, 8)
+
+
+FUSED_REFINE_CALLS = [0]   # launches of the fused kernel (tests: the path taken)
+
+
+def boundary_refine_fused(em: EdgeMap, blend, w1, s1, t1, w2_frag, s2, t2, w3, b3) -> torch.Tensor:
+    """The stage after the edge map in one kernel (eval BatchNorm folded, ReLU, bf16 intermediates)."""
+    N, _, H, W = em.x.shape
+    out = torch.empty_like(em.x)
+    L.check(L.lib().hiseg_boundary_refine_fused(
+        em.x.data_ptr(), N, H, W, em.e_raw.data_ptr(), em.mnmx.data_ptr(), blend.data_ptr(), w1.data_ptr(),
+        s1.data_ptr(), t1.data_ptr(), w2_frag.data_ptr(), s2.data_ptr(), t2.data_ptr(), w3.data_ptr(), b3.data_ptr(),
+        out.data_ptr(), L.stream_ptr()), "boundary_refine_fused")
+    FUSED_REFINE_CALLS[0] += 1
+    return out

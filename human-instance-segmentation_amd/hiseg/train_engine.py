@@ -1108,6 +1108,8 @@ def hier_head_train(T: Tape, head: nn.Module, feat: Act):
              "pw2_bwd")
         T.mark(t)
     T.push(back)
+    if head.use_boundary_refinement:   # the returned masks only; bgfg / tn stay the base head's (refinement.py:767-769)
+        logits = boundary_refine_train(T, head.boundary_refiner, logits)
 
     # auxiliary heads on the shared features (refinement.py:760-800)
     if head.use_contour_detection:
@@ -1134,6 +1136,90 @@ def hier_head_train(T: Tape, head: nn.Module, feat: Act):
                 "fg_attention": att.t.view(N, att.H, att.W, att.cstride)[..., :att.C].permute(0, 3, 1, 2),
                 "shared_features": s.t.view(N, s.H, s.W, s.cstride)[..., :s.C].permute(0, 3, 1, 2)})
     return logits, aux
+
+
+def boundary_refine_train(T: Tape, mod: nn.Module, x: torch.Tensor) -> torch.Tensor:
+    """BoundaryRefinementModule.forward (refinement.py:131-149) on the tape, x the base logits [N,3,H,W] f32.
+
+    The backward turns T.ctx["dlogits"] -- the gradient of the refined logits when the stage's ops start -- into the
+    gradient of the base logits: back_blend (runs first) writes dR, dblend and the global sums, the conv ops leave
+    their data gradient on the channel-last copy of x, back_edge (runs last) adds the three paths into x's gradient
+    (include/hiseg_refine.h).  No host synchronisation: mn, mx, blend and the sums stay on the device."""
+    S, lib = T.S, L.lib()
+    ec = mod.edge_conv
+    em = ops.edge_map(x, cl_dtype=S.dtype, want_probs=True)
+    N, _, H, W = em.x.shape
+    xcl = em.x_cl
+    held: Dict[str, torch.Tensor] = {}
+
+    def back_edge():
+        g = T.ctx["dlogits"]
+        gcl = T.grads[id(xcl)] if T.has(xcl) else None
+        dx = torch.empty_like(em.x)
+        _chk(lib.hiseg_edge_map_bwd(g.data_ptr(), gcl.ptr() if gcl is not None else None, hdtype(S.dtype),
+                                    gcl.cstride if gcl is not None else 0, em.probs.data_ptr(), em.e_raw.data_ptr(),
+                                    em.mnmx.data_ptr(), N, H, W, held["ws"].data_ptr(), dx.data_ptr(), _stream()),
+             "edge_map_bwd")
+        T.ctx["dlogits"] = dx
+    T.push(back_edge)
+    h = conv_bn_act(T, ec[0], ec[1], act_of(ec[2]), xcl)
+    h = conv_bn_act(T, ec[3], ec[4], act_of(ec[5]), h)
+    R = Act.new(N, H, W, 3, torch.float32, em.x.device)
+    conv_plain(T, ec[6], ACT_NONE, h, out=R)
+    bw = mod.blend_weight
+    assert bw.dtype == torch.float32 and bw.device == em.x.device
+    out, _ = ops.boundary_blend(em, R, bw)
+
+    def back_blend():
+        g = T.ctx["dlogits"]
+        gR, acc = T.grad(R)
+        assert not acc
+        ws = torch.empty(int(lib.hiseg_boundary_bwd_ws(N, H, W)), dtype=torch.float32, device=em.x.device)
+        held["ws"] = ws
+        db = S.grad(bw) if bw.requires_grad else None
+        _chk(lib.hiseg_boundary_blend_bwd(g.data_ptr(), R.ptr(), R.cstride, em.e_raw.data_ptr(), em.mnmx.data_ptr(),
+                                          bw.data_ptr(), N, H, W, gR.ptr(), gR.cstride, _ptr(db), ws.data_ptr(),
+                                          _stream()), "boundary_blend_bwd")
+        T.mark(R)
+    T.push(back_blend)
+    return out
+
+
+class _RefineFunction(torch.autograd.Function):
+    """A stand-alone BoundaryRefinementModule in train mode as one autograd node (the module inside the model runs
+    on the ROI path's tape instead)."""
+
+    @staticmethod
+    def forward(ctx, handle, x, *params):
+        mod, S = handle["module"], handle["state"]
+        T = Tape(S)
+        S.begin_step()
+        S.pack()
+        out = boundary_refine_train(T, mod, x)
+        S.flush_counters()
+        ctx.tape, ctx.state = T, S
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        T, S = ctx.tape, ctx.state
+        S.flat.prepare_backward()
+        T.ctx["dlogits"] = g.contiguous().float()
+        T.run_backward()
+        return (None, T.ctx["dlogits"]) + tuple(None for _ in range(len(ctx.needs_input_grad) - 2))
+
+
+def boundary_refine_module_train(mod: nn.Module, x: torch.Tensor) -> torch.Tensor:
+    """Train-mode forward of a stand-alone BoundaryRefinementModule (its parameters move into a flat buffer of
+    their own, as a model's do)."""
+    EG._check_input(x, "BoundaryRefinementModule")
+    dtype = EG._root_dtype(mod)
+    S = mod.__dict__.get("_hiseg_train")
+    if S is None or S.dtype != dtype or S.device != x.device:
+        S = TrainState(mod, dtype, x.device)
+        mod.__dict__["_hiseg_train"] = S
+    handle = {"module": mod, "state": S}
+    return _RefineFunction.apply(handle, x, *[p for _, p in S.flat.named])
 
 
 def _resize_train(T: Tape, a: Act, H: int, W: int) -> torch.Tensor:
