@@ -23,6 +23,7 @@
 // NW (waves = 32-Cout groups per workgroup): 4 -> 128 Cout x 256 pixels, two workgroups per CU; 8 -> 256 Cout x 256
 // pixels, one workgroup per CU (the 256-Cout layers read each halo once instead of once per 128-Cout workgroup).
 #include "conv_common.h"
+#include "head2.h"
 
 namespace hiseg {
 
@@ -72,8 +73,12 @@ __device__ __forceinline__ void hc_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned l
 // R3 (variant 108, round 6): a ring of three halo buffers (72 KiB of LDS, two workgroups per CU still fit): slice
 // sl + 2's halo is LDS-DMA'd during slice sl, so each slice's pieces have a whole slice more to land before the barrier
 // that needs them.
+// H2 (round 7): a trailing 1x1 conv Cout -> 2 in place of the output store (d.head2_w / head2_b / head2_out,
+// include/hiseg.h): the workgroup holds every output channel of its 256 pixels (Cout == BCO == 128), so after the
+// conversion barrier thread t reads tile row t from LDS and sums its 128 bf16 values against the two weight rows
+// (head2_acc, the loop of hier_combine_kernel) and stores 8 bytes; the 64-KiB bf16 tile never leaves the CU.
 template <int ACT, bool RES, int NW, bool UP = false, int ABL = 0, bool RP = false, bool ST = false, int TWB = 1,
-          bool BR = false, bool R3 = false>
+          bool BR = false, bool R3 = false, bool H2 = false>
 __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(ConvArgs a) {
   constexpr int NCG = NW / TWB;                      // Cout groups of 32
   constexpr int BCO = 32 * NCG, TM = 2, NR = 16;    // wave tile: 32 Cout x (16 rows x 16 columns)
@@ -87,6 +92,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
   constexpr int NPX = 256 * TWB;                      // output pixels of the tile
   static_assert((NW == 4 || NW == 8) && (TWB == 1 || (TWB == 2 && NW == 4 && !RP)), "configuration");
   static_assert(!R3 || (NW == 4 && !RP && TWB == 1 && !ST && !BR), "R3: the plain / residual 128-Cout form");
+  static_assert(!H2 || (NW == 4 && TWB == 1 && !ST && !BR && !UP && !RP && ABL == 0), "H2: the 128-Cout one-block form");
   // halo pieces the last wave issues per slice (the fewest of any wave): the vmcnt bound that still waits for every
   // piece of an older slice
   constexpr int NPMIN = ((NHR + 15) / 16 - 1 - (NW - 1)) / NW + 1;
@@ -373,6 +379,12 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
     return;
   }
   char* tile = reinterpret_cast<char*>(smem);
+  // H2: the two weight rows [2][128] f32 are read through the constant address space (read-only for the whole
+  // launch), so they arrive by scalar loads and feed the multiply-adds as SGPR operands: a table in LDS cost four
+  // 16-B reads per chunk and thread beside the one that fetches the tile row (128->128 @128x96 x 256 ROIs in the
+  // benchmark's trace: 919 vs 882 us, profiles/r7_head_fusion_ab.txt)
+  typedef const __attribute__((address_space(4))) float* h2_cptr;
+  h2_cptr h2w = (h2_cptr)(uintptr_t)d.head2_w;
   if constexpr (RES && !RP) {
 #pragma unroll
     for (int k = 0; k < NRI; ++k) res_dma(k);
@@ -441,6 +453,24 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
     convert(std::integral_constant<int, 0>{}, std::integral_constant<int, NR>{});
   }
   __syncthreads();
+  if constexpr (H2) {   // thread t = tile row t: (t0, t1) of its pixel; nothing else is stored
+    const int px = px_of(t);
+    float t0 = d.head2_b[0], t1 = d.head2_b[1];
+#pragma unroll
+    for (int c = 0; c < CPR; ++c) {
+      float v[8];
+      Chunk<bf16_t>::unpack(*reinterpret_cast<const uint4*>(tile + t * EROWB + ((c ^ (t & SWM)) << 4)), v);
+      float w0[8], w1[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        w0[e] = h2w[8 * c + e];
+        w1[e] = h2w[BCO + 8 * c + e];
+      }
+      head2_acc<8>(t0, t1, w0, w1, v);
+    }
+    if (px >= 0) *reinterpret_cast<float2*>(d.head2_out + 2ll * px) = make_float2(t0, t1);
+    return;
+  }
   constexpr int NST = NPX * CPR / (NW * 64);   // NPX rows x CPR chunks over the workgroup's threads
   // ST: thread t stores chunk t % CPR (8 channels) of rows t / CPR + 16 k: 16 pixels of those channels pass through its
   // registers; it sums them shifted by its first valid value (shifted sums: no division in the loop, no cancellation
@@ -579,7 +609,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
 }
 
 template <int ACT, bool RES, int NW, bool UP = false, int ABL = 0, bool RP = false, bool ST = false, int TWB = 1,
-          bool BR = false, bool R3 = false>
+          bool BR = false, bool R3 = false, bool H2 = false>
 static int launch_hwc(const ConvArgs& a, hipStream_t s) {
   const hiseg_conv2d_desc& d = a.d;
   constexpr int BCO = 32 * NW / TWB, TW = 16 * TWB;
@@ -589,7 +619,7 @@ static int launch_hwc(const ConvArgs& a, hipStream_t s) {
   const int nco = d.Cout_pad / BCO;
   const size_t halo = R3 ? halo2 / 2 * 3 : halo2;
   const size_t lds = RP ? (size_t)80 * 1024 : (halo > epi ? halo : epi);
-  auto kern = conv_hwc_kernel<ACT, RES, NW, UP, ABL, RP, ST, TWB, BR, R3>;
+  auto kern = conv_hwc_kernel<ACT, RES, NW, UP, ABL, RP, ST, TWB, BR, R3, H2>;
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -978,7 +1008,17 @@ static bool conv_hwc_applies(const ConvArgs& a, int variant) {
        !d.bnb_scale || !d.bnb_shift || !d.bnb_mean || !d.bnb_invstd ||
        (d.bnb_act != HISEG_ACT_RELU && d.bnb_act != HISEG_ACT_NONE)))
     return false;
+  // the trailing 1x1 in the epilogue (H2): one 128-Cout workgroup per pixel block, the residual form, variants 104 / 108
+  if (d.head2_out &&
+      ((variant != 104 && variant != 108) || d.Cout != 128 || !d.residual || d.a_up != 1 || d.stats_partial ||
+       d.bnb_partial || !d.head2_w || !d.head2_b || ((uintptr_t)d.head2_out & 7)))
+    return false;
   return true;
+}
+
+// Whether the automatic choice's variant (r3: 108, else 104) takes the layer with its head2 epilogue.
+bool conv_hwc_head2_applies(const ConvArgs& a, bool r3) {
+  return a.d.head2_out != nullptr && conv_hwc_applies(a, r3 ? 108 : 104);
 }
 
 // BatchNorm statistics partials the automatic choice would fuse into this layer's epilogue (0: none): the pixel tiles
@@ -1038,6 +1078,16 @@ int conv_hwc_try(const ConvArgs& a, hipStream_t s, int variant) {
     else
       r = d.a_up == 2 ? launch_hwc<HISEG_ACT_NONE, false, 4, true, 0, false, true>(a, s)
                       : launch_hwc<HISEG_ACT_NONE, false, 4, false, 0, false, true>(a, s);
+    return r < 0 ? r : 1;
+  }
+  if (d.head2_out) {   // the trailing-1x1 epilogue (variants 104 / 108, residual; conv_hwc_applies checked the form)
+    const bool relu = d.act == HISEG_ACT_RELU;
+    const int r =
+        variant == 108
+            ? (relu ? launch_hwc<HISEG_ACT_RELU, true, 4, false, 0, false, false, 1, false, true, true>(a, s)
+                    : launch_hwc<HISEG_ACT_NONE, true, 4, false, 0, false, false, 1, false, true, true>(a, s))
+            : (relu ? launch_hwc<HISEG_ACT_RELU, true, 4, false, 0, false, false, 1, false, false, true>(a, s)
+                    : launch_hwc<HISEG_ACT_NONE, true, 4, false, 0, false, false, 1, false, false, true>(a, s));
     return r < 0 ? r : 1;
   }
   const int r = variant == 109 ? launch_hwc_mt_act<1, HISEG_CONV_HWC_MT>(a, s)

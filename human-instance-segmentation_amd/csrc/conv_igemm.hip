@@ -502,6 +502,7 @@ int conv_hwr_try(const ConvArgs& a, hipStream_t s, int variant);
 int conv_hwt_try(const ConvArgs& a, hipStream_t s, int variant);
 int conv_hwc_try(const ConvArgs& a, hipStream_t s, int variant);
 int conv_hwc_stats_tiles(const ConvArgs& a);
+bool conv_hwc_head2_applies(const ConvArgs& a, bool r3);
 int conv_small_try(const ConvArgs& a, hipStream_t s, int variant);
 int conv_rows_try(const ConvArgs& a, hipStream_t s, int variant);
 bool conv_pw_applies(const ConvArgs& a);
@@ -583,6 +584,22 @@ extern "C" int hiseg_conv2d_stats_tiles(const hiseg_conv2d_desc* d) {
   return conv_hwc_stats_tiles(a);
 }
 
+extern "C" int hiseg_conv2d_fused_ok(const hiseg_conv2d_desc* d) {
+  if (d == nullptr || d->dtype != HISEG_BF16 || d->N <= 0 || (!d->px_scale && !d->head2_out) ||
+      (d->px_scale && d->head2_out) || d->stats_partial || d->bnb_partial || d->a_up != 1 || d->K_pad % 64)
+    return 0;
+  const long long M = (long long)d->N * d->Ho * d->Wo;
+  if (M >= (1ll << 31)) return 0;
+  ConvArgs a;
+  a.d = *d;
+  a.M = (int)M;
+  a.Cin = d->Ca + d->Cb;
+  a.nK = d->K_pad / 64;
+  a.Hs = d->H;
+  a.Ws = d->W;
+  return d->px_scale ? (conv_pw_applies(a) ? 1 : 0) : (conv_hwc_head2_applies(a, hwc_r3_mode()) ? 1 : 0);
+}
+
 extern "C" int hiseg_conv2d_fwd_variant(const hiseg_conv2d_desc* d, int variant, hiseg_stream_t stream) {
 #ifndef HISEG_DIAG
   HISEG_REQUIRE(release_variant(variant), HISEG_ERR_BAD_ARG,
@@ -595,7 +612,11 @@ static int conv2d_impl(const hiseg_conv2d_desc* d, hiseg_stream_t stream, int va
   HISEG_REQUIRE(d != nullptr, HISEG_ERR_BAD_ARG, "conv2d: null descriptor");
   HISEG_REQUIRE(d->dtype == HISEG_F32 || d->dtype == HISEG_BF16, HISEG_ERR_BAD_DTYPE, "conv2d: dtype %d", d->dtype);
   HISEG_REQUIRE(d->out_dtype == HISEG_F32 || d->out_dtype == HISEG_BF16, HISEG_ERR_BAD_DTYPE, "conv2d: out_dtype %d", d->out_dtype);
-  HISEG_REQUIRE(d->srcA && d->weight && d->scale && d->shift && d->out, HISEG_ERR_BAD_ARG, "conv2d: null pointer");
+  HISEG_REQUIRE(d->srcA && d->weight && d->scale && d->shift && (d->out || d->head2_out), HISEG_ERR_BAD_ARG,
+                "conv2d: null pointer");
+  HISEG_REQUIRE(!(d->px_scale || d->head2_out) || (variant == 0 && !d->stats_partial && !d->bnb_partial &&
+                                                   !(d->px_scale && d->head2_out)),
+                HISEG_ERR_BAD_ARG, "conv2d: px_scale / head2_out go with the automatic choice alone, one at a time");
   HISEG_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ho > 0 && d->Wo > 0, HISEG_ERR_BAD_SHAPE, "conv2d: empty grid");
   HISEG_REQUIRE(d->KH > 0 && d->KW > 0 && d->stride > 0 && d->pad >= 0, HISEG_ERR_BAD_SHAPE, "conv2d: bad window");
   HISEG_REQUIRE(d->a_up == 1 || d->a_up == 2, HISEG_ERR_BAD_SHAPE, "conv2d: a_up must be 1 or 2");
@@ -681,6 +702,8 @@ static int conv2d_impl(const hiseg_conv2d_desc* d, hiseg_stream_t stream, int va
         c.out = const_cast<void*>(at(d->out, out_px * d->o_cstride * eo));
         c.out2 = const_cast<void*>(at(d->out2, out_px * d->o2_cstride * ea));
         if (d->in_scale) c.in_scale = d->in_scale + (long long)n0 * d->Ca;   // per-image SE gate [N][Ca]
+        if (d->px_scale) c.px_scale = d->px_scale + n0 * in_px;              // per-pixel scale of source A
+        if (d->head2_out) c.head2_out = d->head2_out + 2 * n0 * out_px;      // [pixels][2]
         const int r = conv2d_impl(&c, stream, variant);
         if (r) return r;
       }
@@ -702,6 +725,14 @@ static int conv2d_impl(const hiseg_conv2d_desc* d, hiseg_stream_t stream, int va
   a.ins_vec = d->in_scale != nullptr && ((uintptr_t)d->in_scale & 15) == 0 && (d->Ca & 3) == 0;
   a.ws = static_cast<float*>(d->workspace);
   a.kper = a.nK;
+  // The fused operands of round 7 exist in one kernel each, and no other kernel may take the layer and silently
+  // ignore them: the caller asks hiseg_conv2d_fused_ok first.
+  if (d->px_scale || d->head2_out) {
+    const int r = d->px_scale ? conv_pw_try(a, s, 90) : conv_hwc_try(a, s, hwc_r3_mode() ? 108 : 104);
+    HISEG_REQUIRE(r != 0, HISEG_ERR_BAD_ARG,
+                  "conv2d: no kernel takes this layer with px_scale / head2_out (hiseg_conv2d_fused_ok)");
+    return r < 0 ? r : HISEG_OK;
+  }
   if (variant == 99 || variant == 0) {
     // split-K generic kernel for small-grid, long-K 1x1 layers (variant 99 forces it when the plan splits)
     const int sp = splitk_plan(a);

@@ -48,7 +48,11 @@ typedef unsigned pw_u2 __attribute__((ext_vector_type(2)));
 // the last) carry an offset beyond num_records: loads return zeros, stores are dropped -- no divergent
 // branches, so the compiler's vmcnt waits stay counted.
 // EPI: 0 plain, 1 residual added before the activation, 2 mul applied after it (include/hiseg.h epilogue).
-template <int NKSA, int EPI, int ACT, bool CONVT, int RB, bool INS>
+// PXS (round 7): the per-pixel twin of INS -- d.px_scale [M] f32, the spatial-attention map of the ConvTranspose's
+// input.  A lane's two pixels' scales are loaded with the block's fragment prefetch and applied to its 8 channels
+// per k-step in registers, in f32, rounded to bf16 as pixel_scale_kernel (misc.hip) does, so the operand -- and the
+// output -- has the bits of the separate pass, which is gone (a read and a write of the whole input).
+template <int NKSA, int EPI, int ACT, bool CONVT, int RB, bool INS, bool PXS = false>
 __global__ void __launch_bounds__(256, 1) conv_pw_kernel(ConvArgs a, int nct, int nks_arg) {
   // NKSA > 0: exactly NKSA k-steps (the head's layers: no run-time guards, which cost the residual / mul
   // forms registers); NKSA < 0: a run-time count nks_arg <= -NKSA
@@ -149,6 +153,16 @@ __global__ void __launch_bounds__(256, 1) conv_pw_kernel(ConvArgs a, int nct, in
   const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<void*>(xp), (short)0, XOP ? (int)(out_px * x_cs * 2) : 0, 0x00020000);
   const bool bch_ok = NKS == 9 && 8 * g < d.Cb;   // this lane's chunk of the source-B k-step holds channels
+  const __amdgpu_buffer_rsrc_t rS = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(PXS ? d.px_scale : d.scale), (short)0, PXS ? (int)((long long)M * 4) : 0, 0x00020000);
+  // the scales of block b's two pixels of this lane (zero past the last pixel, where the fragments are zero too)
+  auto load_ps = [&](int b, float (&ps)[2]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int p = b * kPwBlk + 16 * j + pl;
+      ps[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rS, p < M ? (unsigned)(p * 4) : OOB, 0, 0));
+    }
+  };
 
   // B fragments of block b: lane (g, pl) holds pixel b*32 + 16j + pl, channels 32 ks + 8 g .. + 7
   auto load_ks = [&](int b, int ks, uint4 (&bk)[2]) __attribute__((always_inline)) {
@@ -206,11 +220,28 @@ __global__ void __launch_bounds__(256, 1) conv_pw_kernel(ConvArgs a, int nct, in
   const int stride = ngrp * 4;
   int b = grp * 4 + w;
   uint4 b0[NKS][2], b1[NKS][2];
+  float ps0[2] = {0.f, 0.f}, ps1[2] = {0.f, 0.f};
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks)
     if (ks < nks) load_ks(b, ks, b0[ks]);
-  auto process = [&](int b, uint4 (&bf)[NKS][2], uint4 (&bn)[NKS][2]) __attribute__((always_inline)) {
+  if constexpr (PXS) load_ps(b, ps0);
+  auto process = [&](int b, uint4 (&bf)[NKS][2], uint4 (&bn)[NKS][2], float (&psf)[2], float (&psn)[2])
+      __attribute__((always_inline)) {
     const int nb = b + stride;
+    if constexpr (PXS) {   // scale the current block's fragments (v * att, one bf16 rounding: pixel_scale_kernel's)
+#pragma unroll
+      for (int ks = 0; ks < NKS; ++ks) {
+        if (ks >= nks) continue;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          float f[8];
+          Chunk<bf16_t>::unpack(bf[ks][j], f);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) f[e] *= psf[j];
+          bf[ks][j] = Chunk<bf16_t>::pack(f);
+        }
+      }
+    }
     if constexpr (INS) {   // gate the current block's fragments before the next block's loads reuse registers
       int gofs[2];
 #pragma unroll
@@ -238,6 +269,7 @@ __global__ void __launch_bounds__(256, 1) conv_pw_kernel(ConvArgs a, int nct, in
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks)
       if (ks < nks) load_ks(nb, ks, bn[ks]);
+    if constexpr (PXS) load_ps(nb, psn);
     set_block(b);
     pw_u2 rv[XOP ? RB : 1][2];
     if constexpr (XOP) {
@@ -295,9 +327,9 @@ __global__ void __launch_bounds__(256, 1) conv_pw_kernel(ConvArgs a, int nct, in
     }
   };
   for (; b < nblk; b += 2 * stride) {
-    process(b, b0, b1);
+    process(b, b0, b1, ps0, ps1);
     if (b + stride >= nblk) break;
-    process(b + stride, b1, b0);
+    process(b + stride, b1, b0, ps1, ps0);
   }
 }
 
@@ -315,11 +347,11 @@ static size_t pw_lds_bytes(int NKS, int RB, bool ins, const hiseg_conv2d_desc& d
   return (size_t)16 * RB * (NKS * 4 + 1) * 16 + 2 * 16 * RB * 4 + (ins ? (size_t)d.N * d.Ca * 4 : 0);
 }
 
-template <int NKSA, int EPI, int ACT, bool CONVT, int RB, bool INS>
+template <int NKSA, int EPI, int ACT, bool CONVT, int RB, bool INS, bool PXS = false>
 static int launch_pw(const ConvArgs& a, hipStream_t s, int nks) {
   const hiseg_conv2d_desc& d = a.d;
   const size_t lds = pw_lds_bytes(NKSA < 0 ? -NKSA : NKSA, RB, INS, d);
-  auto kern = conv_pw_kernel<NKSA, EPI, ACT, CONVT, RB, INS>;
+  auto kern = conv_pw_kernel<NKSA, EPI, ACT, CONVT, RB, INS, PXS>;
   static int occ = 0;   // resident workgroups per CU at the largest LDS request seen (the gate table varies)
   static size_t occ_lds = 0;
   if (lds > occ_lds) {
@@ -400,6 +432,11 @@ static int launch_pw_k(const ConvArgs& a, hipStream_t s, int nks) {
            : act == SI ? launch_pw<-NKS, 0, SI, false, 16, false>(a, s, nks)
                        : launch_pw<-NKS, 0, N, false, 16, false>(a, s, nks);
     }
+    if constexpr (NKS == 8) {   // the head's 256 -> 4 x 128 ConvTranspose behind the spatial attention (pw_plan)
+      if (d.convT && d.px_scale) return act == R ? launch_pw<NKS, 0, R, true, 16, false, true>(a, s, nks)
+                                                 : launch_pw<NKS, 0, N, true, 16, false, true>(a, s, nks);
+    }
+    HISEG_REQUIRE(!d.px_scale, HISEG_ERR_BAD_ARG, "conv_pw: px_scale needs the 8-k-step ConvTranspose form");
     if (d.convT) return act == R ? launch_pw<NKS, 0, R, true, 16, false>(a, s, nks)
                                  : launch_pw<NKS, 0, N, true, 16, false>(a, s, nks);
     if (d.residual) return act == R ? launch_pw<NKS, 1, R, false, 16, false>(a, s, nks)
@@ -450,6 +487,10 @@ static bool pw_plan(const ConvArgs& a, int& rb, int& nks, int& nks_max) {
       if (!(want > 4 && nks > 8)) rb = want;
     }
   }
+  // per-pixel input scale: the 256-column-tile ConvTranspose at exactly 8 k-steps, ReLU or no activation
+  if (d.px_scale && (!d.convT || rb != 16 || nks != 8 || d.Ca != 256 || d.in_scale || ((uintptr_t)d.px_scale & 3) ||
+                     (d.act != HISEG_ACT_NONE && d.act != HISEG_ACT_RELU)))
+    return false;
   const bool comb = rb == 16 && nks == 9;
   if ((rb == 16 && nks > 9) || (rb > 4 && nks > 8)) return false;   // (registers: 2 x 10 B fragment sets)
   if (comb ? (d.Ca != 256 || d.Cb > 32 || d.convT || d.residual || d.mul || d.in_scale ||

@@ -3,6 +3,7 @@
 // (cdna_hip_programming.md Guideline 13) and grid-sized for 256 CUs.
 #include <float.h>
 #include "common.h"
+#include "head2.h"
 
 namespace hiseg {
 
@@ -895,7 +896,9 @@ __global__ void __launch_bounds__(256) input_norm_kernel(const float* x, int B, 
 }
 
 // ------------------------------------------------------------------ hierarchical combine
-template <typename T>
+// TN2: the target branch's last 1x1 was applied by the producing conv's epilogue (hiseg_conv2d_desc.head2_out):
+// tfeat is then f32 [N * 2h * 2w][2], the pixel's (t0, t1); t_w / t_b are not read.
+template <typename T, bool TN2 = false>
 __global__ void __launch_bounds__(256) hier_combine_kernel(const float* low, int N, int h, int w, const void* tfeat, int Ct,
                                                            const float* ut_w, const float* ut_scale, const float* ut_shift,
                                                            int ut_act, float ut_beta, int ut_ns, const float* u1_w,
@@ -906,7 +909,8 @@ __global__ void __launch_bounds__(256) hier_combine_kernel(const float* low, int
   for (int i = t; i < 256; i += 256) s_ut[i] = ut_w[i];
   if (t < 32 && !ut_ns) { s_us[t] = ut_scale[t]; s_ush[t] = ut_shift[t]; }
   if (t < 64) s_u1[t] = u1_w[t];
-  for (int i = t; i < 2 * Ct; i += 256) s_tw[i] = t_w[i];
+  if constexpr (!TN2)
+    for (int i = t; i < 2 * Ct; i += 256) s_tw[i] = t_w[i];
   __syncthreads();
   const int H = 2 * h, W = 2 * w;
   const long long gid = (long long)blockIdx.x * 256 + t;
@@ -931,14 +935,19 @@ __global__ void __launch_bounds__(256) hier_combine_kernel(const float* low, int
     b1 += s_u1[32 + co] * hsum;
   }
   constexpr int K = Chunk<T>::N;
-  float t0 = t_b[0], t1 = t_b[1], v[K];
-  const uint4* tf = reinterpret_cast<const uint4*>(tfeat) + gid * (Ct / K);
-  for (int ch = 0; ch < Ct / K; ++ch) {
-    Chunk<T>::unpack(tf[ch], v);
-#pragma unroll
-    for (int e = 0; e < K; ++e) {
-      t0 += s_tw[ch * K + e] * v[e];
-      t1 += s_tw[Ct + ch * K + e] * v[e];
+  float t0, t1;
+  if constexpr (TN2) {
+    const float2 tq = reinterpret_cast<const float2*>(tfeat)[gid];
+    t0 = tq.x;
+    t1 = tq.y;
+  } else {
+    t0 = t_b[0];
+    t1 = t_b[1];
+    float v[K];
+    const uint4* tf = reinterpret_cast<const uint4*>(tfeat) + gid * (Ct / K);
+    for (int ch = 0; ch < Ct / K; ++ch) {
+      Chunk<T>::unpack(tf[ch], v);
+      head2_acc<K>(t0, t1, s_tw + ch * K, s_tw + Ct + ch * K, v);
     }
   }
   const float mx = fmaxf(b0, b1);
@@ -1100,6 +1109,27 @@ extern "C" int hiseg_attn_spatial_fwd(int dtype, const void* x, int N, int H, in
   const long long tot = P * (C / chunk_of(dtype));
   DISPATCH_T(dtype, pixel_scale_kernel, dim3(nblocks(tot, 256)), dim3(256), 0, s, x, P, C, att, out);
   return hiseg_check_launch("attn_spatial");
+}
+
+extern "C" int hiseg_attn_map_fwd(int dtype, const void* x, int N, int H, int W, int C, const float* w7, int k,
+                                  float* stats, float* att, hiseg_stream_t stream) {
+  HISEG_REQUIRE(x && w7 && stats && att && N > 0 && H > 0 && W > 0 && C > 0 && (k & 1), HISEG_ERR_BAD_ARG,
+                "attn_map: bad args");
+  HISEG_REQUIRE(C % chunk_of(dtype) == 0, HISEG_ERR_BAD_SHAPE, "attn_map: C must be chunk aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const long long P = (long long)N * H * W;
+  DISPATCH_T(dtype, attn_stats_kernel, dim3(nblocks(P * 16, 256)), dim3(256), 0, s, x, P, C, stats);
+  hipLaunchKernelGGL(attn_map_kernel, dim3(nblocks(P, 256)), dim3(256), 0, s, stats, N, H, W, w7, k, att);
+  return hiseg_check_launch("attn_map");
+}
+
+extern "C" int hiseg_pixel_scale_fwd(int dtype, const void* x, long long P, int C, const float* att, void* out,
+                                     hiseg_stream_t stream) {
+  HISEG_REQUIRE(x && att && out && P > 0 && C > 0, HISEG_ERR_BAD_ARG, "pixel_scale: bad args");
+  HISEG_REQUIRE(C % chunk_of(dtype) == 0, HISEG_ERR_BAD_SHAPE, "pixel_scale: C must be chunk aligned");
+  const long long tot = P * (C / chunk_of(dtype));
+  DISPATCH_T(dtype, pixel_scale_kernel, dim3(nblocks(tot, 256)), dim3(256), 0, (hipStream_t)stream, x, P, C, att, out);
+  return hiseg_check_launch("pixel_scale");
 }
 
 extern "C" int hiseg_gap_splits(int HW) {
@@ -1378,6 +1408,21 @@ extern "C" int hiseg_hier_combine_fwd(int dtype, const float* low, int N, int h,
              Ct, ut_w, ut_scale, ut_shift, ut_act, ut_beta, ut_per_sample ? 32 : 0, u1_w, u1_b, t_w, t_b, logits, bgfg,
              tn);
   return hiseg_check_launch("hier_combine");
+}
+
+extern "C" int hiseg_hier_combine_tn_fwd(const float* low, int N, int h, int w, const float* tn2, const float* ut_w,
+                                         const float* ut_scale, const float* ut_shift, int ut_act, float ut_beta,
+                                         int ut_per_sample, const float* u1_w, const float* u1_b, float* logits,
+                                         float* bgfg, float* tn, hiseg_stream_t stream) {
+  HISEG_REQUIRE(low && tn2 && ut_w && ut_scale && ut_shift && u1_w && u1_b && logits, HISEG_ERR_BAD_ARG,
+                "hier_combine_tn: null pointer");
+  HISEG_REQUIRE(N >= 0 && h > 0 && w > 0 && ((uintptr_t)tn2 & 7) == 0, HISEG_ERR_BAD_SHAPE, "hier_combine_tn: bad shape");
+  if (N == 0) return HISEG_OK;
+  const long long total = (long long)N * 4 * h * w;
+  hipLaunchKernelGGL((hier_combine_kernel<float, true>), dim3(nblocks(total, 256)), dim3(256), 0, (hipStream_t)stream, low,
+                     N, h, w, (const void*)tn2, 0, ut_w, ut_scale, ut_shift, ut_act, ut_beta, ut_per_sample ? 32 : 0, u1_w,
+                     u1_b, (const float*)nullptr, (const float*)nullptr, logits, bgfg, tn);
+  return hiseg_check_launch("hier_combine_tn");
 }
 
 // LayerNorm2d over upsample_bg_fg's ConvTranspose2d(2, 32, 2, s2) output z (model.py:18-38 at

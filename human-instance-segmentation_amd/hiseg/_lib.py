@@ -142,6 +142,8 @@ class Conv2dDesc(Desc):
         ("bnb_partial", c_void_p), ("bnb_z", c_void_p), ("bnb_z_cstride", c_int), ("bnb_z_coff", c_int),
         ("bnb_scale", c_void_p), ("bnb_shift", c_void_p), ("bnb_mean", c_void_p), ("bnb_invstd", c_void_p),
         ("bnb_act", c_int),
+        ("px_scale", c_void_p),
+        ("head2_w", c_void_p), ("head2_b", c_void_p), ("head2_out", c_void_p),
     ]
 
 
@@ -269,6 +271,11 @@ def _declare(lib):
         "hiseg_conv2d_workspace_bytes": ([ctypes.POINTER(Conv2dDesc)], c_ll),
         "hiseg_maxpool2x2_fwd": ([c_int, P, c_int, c_int, c_int, c_int, P, P], c_int),
         "hiseg_attn_spatial_fwd": ([c_int, P, c_int, c_int, c_int, c_int, P, c_int, P, P, P, P], c_int),
+        "hiseg_attn_map_fwd": ([c_int, P, c_int, c_int, c_int, c_int, P, c_int, P, P, P], c_int),
+        "hiseg_pixel_scale_fwd": ([c_int, P, c_ll, c_int, P, P, P], c_int),
+        "hiseg_conv2d_fused_ok": ([ctypes.POINTER(Conv2dDesc)], c_int),
+        "hiseg_hier_combine_tn_fwd": ([P, c_int, c_int, c_int, P, P, P, P, c_int, c_float, c_int, P, P, P, P, P, P],
+                                      c_int),
         "hiseg_gap_splits": ([c_int], c_int),
         "hiseg_se_gate_fwd": ([c_int, P, c_int, c_int, c_int, P, P, c_int, P, P, c_int, c_float, P, P, P], c_int),
         "hiseg_channel_scale_fwd": ([c_int, P, c_int, c_int, c_int, P, P, P], c_int),

@@ -10,8 +10,9 @@ libhiseg call per fused layer:
   memory: the conv loader reads its K range from two sources (and upsamples source A ×2 for
   the smp decoder);
 * the trainable 1→2 output_conv of the pretrained-UNet wrapper is fused into the RoIAlign
-  gather, the whole upsample_bg_fg branch and the target branch's last 1×1 into the
-  hierarchical combine kernel.
+  gather, the whole upsample_bg_fg branch into the hierarchical combine kernel, the target
+  branch's last 1×1 into the epilogue of the conv before it (or the combine kernel where that
+  conv has no such form) and its spatial-attention multiply into the ConvTranspose's loader.
 
 Packed weights ("plans") are cached per model, compute dtype and device and rebuilt when
 any parameter or buffer changes (tensor version counters).  Activations are NHWC.
@@ -159,11 +160,15 @@ def _check_input(x: torch.Tensor, what: str):
 
 
 # ------------------------------------------------------------------------------------ blocks
-def residual_block(E: Ctx, blk: nn.Module, x: Act, out: Optional[Act] = None) -> Act:
-    """ResidualBlock (refinement.py:31-55 / unet.py:35-58): two fused launches."""
+def residual_block(E: Ctx, blk: nn.Module, x: Act, out: Optional[Act] = None,
+                   head2: Optional[ops.Head2] = None) -> Optional[Act]:
+    """ResidualBlock (refinement.py:31-55 / unet.py:35-58): two fused launches.  ``head2``: a 1x1 -> 2 that alone
+    consumes the block's output (ops.Head2); returns None when conv2's epilogue applied it."""
     a1 = act_code(blk.activation1 if hasattr(blk, "activation1") else blk.activation)
     a2 = act_code(blk.activation2 if hasattr(blk, "activation2") else blk.activation)
     h = cna(E, blk.conv1, blk.norm1, a1, x)
+    if head2 is not None and out is None and not isinstance(blk.norm2, LayerNorm2d):
+        return ops.conv2d(E.conv(blk.conv2, blk.norm2, a2), h, residual=x, head2=head2)
     return cna(E, blk.conv2, blk.norm2, a2, h, residual=x, out=out)
 
 
@@ -240,22 +245,29 @@ def hier_head(E: Ctx, head: nn.Module, feat: Act, aux: str) -> Tuple[torch.Tenso
     tb = bh.target_vs_nontarget_branch
     if bh.use_attention_module:
         t = residual_block(E, tb[0], gated)
-        t = ops.attn_spatial(t, E.f32(tb[1].conv.weight))
-        t = cna(E, tb[3], tb[4], act_code(tb[5]), t, convT=True)
+        if isinstance(tb[4], LayerNorm2d):
+            t = ops.attn_spatial(t, E.f32(tb[1].conv.weight))
+            t = cna(E, tb[3], tb[4], act_code(tb[5]), t, convT=True)
+        else:   # the attention multiply rides in the ConvTranspose's loader (ops.conv2d px_scale)
+            att = ops.attn_map(t, E.f32(tb[1].conv.weight))
+            t = ops.conv2d(E.convT(tb[3], tb[4], act_code(tb[5])), t, px_scale=att)
         ca = tb[6]
         gate = ops.se_gate(t, E.f32(ca.fc1.weight, (ca.fc1.out_channels, ca.fc1.in_channels)), None,
                            E.f32(ca.fc2.weight, (ca.fc2.out_channels, ca.fc2.in_channels)), None,
                            act_code(ca.activation))
         t = ops.channel_scale(t, gate)
-        t = residual_block(E, tb[8], t)
-        last = tb[9]
+        blk, last = tb[8], tb[9]
     else:
         t = residual_block(E, tb[0], gated)
         t = cna(E, tb[2], tb[3], act_code(tb[4]), t, convT=True)
-        t = residual_block(E, tb[6], t)
-        last = tb[7]
+        blk, last = tb[6], tb[7]
+    # the branch's last residual block feeds only its last 1x1 (-> 2), which rides in conv2's epilogue where the
+    # layer has that form (ops.Head2): t is then None and h2.out the two target logits per pixel
+    h2 = ops.Head2(E.f32(last.weight, (2, last.in_channels)), E.f32(last.bias))
+    tH, tW = t.H, t.W
+    t = residual_block(E, blk, t, head2=h2)
     mh, mw = bh.mask_height, bh.mask_width
-    if (t.H, t.W) != (mh, mw) or (2 * low.H, 2 * low.W) != (mh, mw):
+    if (tH, tW) != (mh, mw) or (2 * low.H, 2 * low.W) != (mh, mw):
         raise NotImplementedError(f"mask size {mh}x{mw} must be 2x the ROI size {low.H}x{low.W} on the hiseg path")
     up = bh.upsample_bg_fg
     per_sample = isinstance(up[1], LayerNorm2d)
@@ -272,7 +284,7 @@ def hier_head(E: Ctx, head: nn.Module, feat: Act, aux: str) -> Tuple[torch.Tenso
     logits, bgfg, tn = ops.hier_combine(
         low.t, low.N, low.H, low.W, t, E.f32(up[0].weight), ut_s, ut_h, act_code(up[2]),
         E.f32(up[3].weight, (2, up[3].in_channels)), E.f32(up[3].bias),
-        E.f32(last.weight, (2, last.in_channels)), E.f32(last.bias), want, per_sample=per_sample)
+        h2.w, h2.b, want, per_sample=per_sample, tn2=h2.out)
     if head.use_boundary_refinement:   # refines the returned masks only; the aux tensors stay (refinement.py:767-769)
         logits = boundary_refine(E, head.boundary_refiner, logits)
     auxd: Dict[str, torch.Tensor] = {}

@@ -276,12 +276,27 @@ def fold_affine(cout: int, bias: Optional[torch.Tensor], bn, device):
     return scale, shift
 
 
+@dataclass
+class Head2:
+    """A trailing 1x1 conv Cout -> 2 for conv2d(head2=...): w f32 [2, Cout], b f32 [2].  After the call ``out`` is
+    its f32 [N*Ho*Wo, 2] result when the conv's epilogue applied it (the conv output itself is then not stored and
+    conv2d returns None), or None when the layer has no such kernel and ran as usual."""
+    w: torch.Tensor
+    b: torch.Tensor
+    out: Optional[torch.Tensor] = None
+
+
 def conv2d(p: ConvPlan, xa: Act, xb: Optional[Act] = None, out: Optional[Act] = None, *, a_up: int = 1,
            residual: Optional[Act] = None, mul: Optional[Act] = None, out2: Optional[Act] = None,
            in_scale: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
-           variant: int = 0, out_cpad: Optional[int] = None, split_k_3x3: bool = False) -> Act:
+           variant: int = 0, out_cpad: Optional[int] = None, split_k_3x3: bool = False,
+           px_scale: Optional[torch.Tensor] = None, head2: Optional[Head2] = None) -> Optional[Act]:
     """hiseg_conv2d_fwd.  Returns the output Act (allocated when ``out`` is None; ``out_cpad``: its channel
     stride, the pad channels zero).
+
+    ``px_scale`` (f32, one value per source pixel): source A is read as bf16(xa * px_scale[pixel]) -- inside the
+    kernel's loader where the layer has that form (hiseg_conv2d_fused_ok), through a pixel_scale pass otherwise; the
+    same bits either way.  ``head2``: see :class:`Head2`.
 
     ``variant`` != 0 forces a kernel variant (hiseg_conv2d_fwd_variant; -1 = generic kernel).  ``split_k_3x3``
     passes the split-K workspace to a 3x3 layer too (images of <= 256 pixels, K >= 1536: the library then splits
@@ -298,13 +313,21 @@ def conv2d(p: ConvPlan, xa: Act, xb: Optional[Act] = None, out: Optional[Act] = 
         Ho = (H + 2 * p.pad - p.kh) // p.stride + 1
         Wo = (W + 2 * p.pad - p.kw) // p.stride + 1
         oH, oW = Ho, Wo
-    if out is None:
+    fused = (px_scale is not None or head2 is not None) and not variant and out is None and out2 is None
+    if fused:
+        assert px_scale is None or head2 is None
+        fused = _fused_ok(p, xa, xb, residual, mul, in_scale, px_scale, head2, out_dtype or dt, a_up)
+    if px_scale is not None and not fused:
+        xa = pixel_scale(xa, px_scale)
+    if head2 is not None:
+        head2.out = None
+    if out is None and not (fused and head2 is not None):
         out = Act.new(xa.N, oH, oW, p.cout, out_dtype or dt, xa.t.device, cpad=out_cpad,
                       zero=None if out_cpad is None else out_cpad != p.cout)
-    assert (out.N, out.H, out.W) == (xa.N, oH, oW), ((out.N, out.H, out.W), (xa.N, oH, oW))
+    assert out is None or (out.N, out.H, out.W) == (xa.N, oH, oW), ((out.N, out.H, out.W), (xa.N, oH, oW))
     assert xa.C <= p.ca and (xb is None or xb.C <= p.cb)
     d = L.Conv2dDesc()
-    d.dtype, d.out_dtype = hdtype(dt), hdtype(out.dtype)
+    d.dtype, d.out_dtype = hdtype(dt), hdtype(out.dtype if out is not None else (out_dtype or dt))
     d.N, d.H, d.W, d.Ho, d.Wo = xa.N, H, W, Ho, Wo
     d.KH, d.KW, d.stride, d.pad = p.kh, p.kw, p.stride, p.pad
     d.srcA, d.a_cstride, d.a_coff, d.Ca, d.a_up = xa, xa.cstride, xa.coff, p.ca, a_up
@@ -318,7 +341,14 @@ def conv2d(p: ConvPlan, xa: Act, xb: Optional[Act] = None, out: Optional[Act] = 
         d.residual, d.r_cstride, d.r_coff = residual, residual.cstride, residual.coff
     if mul is not None:
         d.mul, d.m_cstride, d.m_coff = mul, mul.cstride, mul.coff
-    d.out, d.o_cstride, d.o_coff = out, out.cstride, out.coff
+    if out is not None:
+        d.out, d.o_cstride, d.o_coff = out, out.cstride, out.coff
+    else:   # (head2 in the epilogue: the output tile is not stored)
+        d.o_cstride, d.o_coff = p.cout, 0
+        head2.out = torch.empty(xa.N * oH * oW, 2, dtype=torch.float32, device=xa.t.device)
+        d.head2_w, d.head2_b, d.head2_out = head2.w, head2.b, head2.out
+    if fused and px_scale is not None:
+        d.px_scale = px_scale
     if out2 is not None:
         assert out2.dtype == dt
         d.out2, d.o2_cstride, d.o2_coff = out2, out2.cstride, out2.coff
@@ -338,7 +368,7 @@ def conv2d(p: ConvPlan, xa: Act, xb: Optional[Act] = None, out: Optional[Act] = 
             d.workspace, d.workspace_bytes = ws, nbytes
     if RECORD is not None:
         dc = d.copy()
-        keep = [t for t in (xa, xb, out, residual, mul, out2, ws) if t is not None]
+        keep = [t for t in (xa, xb, out, residual, mul, out2, ws, px_scale) if t is not None]
         flops = 2.0 * d.N * d.Ho * d.Wo * p.gemm_cols * p.kh * p.kw * (xa.C + (xb.C if xb is not None else 0))
         RECORD.append((dc, keep, p, flops))
     gate = GATE
@@ -352,6 +382,44 @@ def conv2d(p: ConvPlan, xa: Act, xb: Optional[Act] = None, out: Optional[Act] = 
         gate.light()
     _launch_conv(d, p, xa, xb, variant)
     return out
+
+
+def _fused_ok(p, xa, xb, residual, mul, in_scale, px_scale, head2, out_dtype, a_up) -> bool:
+    """Whether the library has a kernel that applies px_scale / head2 inside this layer (planning only, no launch)."""
+    if xa.dtype != torch.bfloat16 or out_dtype != torch.bfloat16 or xb is not None or mul is not None or \
+            in_scale is not None or a_up != 1:
+        return False
+    if px_scale is not None:
+        assert px_scale.dtype == torch.float32 and px_scale.is_contiguous() and px_scale.numel() == xa.N * xa.H * xa.W
+    if head2 is not None:
+        if p.convT or residual is None:
+            return False
+        assert head2.w.dtype == torch.float32 and head2.w.is_contiguous() and tuple(head2.w.shape) == (2, p.cout)
+        assert head2.b.dtype == torch.float32 and head2.b.numel() == 2
+    d = L.Conv2dDesc()
+    d.dtype = d.out_dtype = L.HISEG_BF16
+    d.N, d.H, d.W = xa.N, xa.H, xa.W
+    if p.convT:
+        d.Ho, d.Wo = xa.H, xa.W
+    else:
+        d.Ho = (xa.H + 2 * p.pad - p.kh) // p.stride + 1
+        d.Wo = (xa.W + 2 * p.pad - p.kw) // p.stride + 1
+    d.KH, d.KW, d.stride, d.pad = p.kh, p.kw, p.stride, p.pad
+    d.srcA, d.a_cstride, d.a_coff, d.Ca, d.a_up = xa, xa.cstride, xa.coff, p.ca, 1
+    d.weight, d.Cout, d.Cout_pad, d.K_pad = p.weight, p.gemm_cols, p.cout_pad, p.k_pad
+    d.scale, d.shift, d.act, d.act_beta = p.scale, p.shift, int(p.act), L.act_beta(p.act)
+    d.o_cstride, d.o_coff = p.cout, 0
+    d.convT = int(p.convT)
+    if p.weight_frag is not None:
+        d.weight_frag = p.weight_frag
+    if residual is not None:
+        d.residual, d.r_cstride, d.r_coff = residual, residual.cstride, residual.coff
+    if px_scale is not None:
+        d.px_scale = px_scale
+        d.out = xa   # (any aligned address: the plan looks at the output's alignment only)
+    if head2 is not None:
+        d.head2_w, d.head2_b, d.head2_out = head2.w, head2.b, head2.w
+    return bool(L.lib().hiseg_conv2d_fused_ok(ctypes.byref(d)))
 
 
 def _launch_conv(d, p, xa, xb, variant=0):
@@ -388,6 +456,26 @@ def attn_spatial(x: Act, w7: torch.Tensor) -> Act:
     L.check(L.lib().hiseg_attn_spatial_fwd(hdtype(x.dtype), x.ptr(), x.N, x.H, x.W, x.C, w7.data_ptr(), k,
                                            stats.data_ptr(), att.data_ptr(), out.ptr(), L.stream_ptr()),
             "attn_spatial")
+    return out
+
+
+def attn_map(x: Act, w7: torch.Tensor) -> torch.Tensor:
+    """The attention map of SpatialAttentionModule alone: sigmoid(conv7x7([mean_c x, max_c x])), f32 [N*H*W]."""
+    assert x.coff == 0 and x.cstride == x.C
+    P = x.N * x.H * x.W
+    stats = torch.empty(P * 2, dtype=torch.float32, device=x.t.device)
+    att = torch.empty(P, dtype=torch.float32, device=x.t.device)
+    L.check(L.lib().hiseg_attn_map_fwd(hdtype(x.dtype), x.ptr(), x.N, x.H, x.W, x.C, w7.data_ptr(), w7.shape[-1],
+                                       stats.data_ptr(), att.data_ptr(), L.stream_ptr()), "attn_map")
+    return att
+
+
+def pixel_scale(x: Act, att: torch.Tensor) -> Act:
+    """x * att[pixel] (attention_modules.py:113); att f32 [N*H*W]."""
+    assert x.coff == 0 and x.cstride == x.C and att.dtype == torch.float32 and att.numel() == x.N * x.H * x.W
+    out = Act.new(x.N, x.H, x.W, x.C, x.dtype, x.t.device, zero=False)
+    L.check(L.lib().hiseg_pixel_scale_fwd(hdtype(x.dtype), x.ptr(), x.N * x.H * x.W, x.C, att.data_ptr(), out.ptr(),
+                                          L.stream_ptr()), "pixel_scale")
     return out
 
 
@@ -461,15 +549,24 @@ def input_norm(images: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, dtyp
     return out
 
 
-def hier_combine(low: torch.Tensor, N: int, h: int, w: int, tfeat: Act, ut_w, ut_scale, ut_shift, ut_act, u1_w, u1_b,
-                 t_w, t_b, want_aux: bool, per_sample: bool = False):
+def hier_combine(low: torch.Tensor, N: int, h: int, w: int, tfeat: Optional[Act], ut_w, ut_scale, ut_shift, ut_act,
+                 u1_w, u1_b, t_w, t_b, want_aux: bool, per_sample: bool = False, tn2: Optional[torch.Tensor] = None):
     """Fused upsample_bg_fg + target 1x1 + hierarchical combine; ``per_sample``: ut_scale/ut_shift are the
-    [N][32] LayerNorm2d tables of hiseg_ubf_ln_tables."""
-    assert tfeat.coff == 0 and tfeat.cstride == tfeat.C and (tfeat.H, tfeat.W) == (2 * h, 2 * w)
+    [N][32] LayerNorm2d tables of hiseg_ubf_ln_tables.  ``tn2`` (f32 [N*2h*2w, 2], conv2d's Head2.out): the target
+    1x1 was applied by the conv that produced tfeat; tfeat / t_w / t_b are then not read."""
     dev = low.device
     logits = torch.empty(N, 3, 2 * h, 2 * w, dtype=torch.float32, device=dev)
     bgfg = torch.empty(N, 2, 2 * h, 2 * w, dtype=torch.float32, device=dev) if want_aux else None
     tn = torch.empty(N, 2, 2 * h, 2 * w, dtype=torch.float32, device=dev) if want_aux else None
+    if tn2 is not None:
+        assert tn2.dtype == torch.float32 and tn2.is_contiguous() and tn2.numel() == N * 4 * h * w * 2
+        L.check(L.lib().hiseg_hier_combine_tn_fwd(low.data_ptr(), N, h, w, tn2.data_ptr(), ut_w.data_ptr(),
+                                                  ut_scale.data_ptr(), ut_shift.data_ptr(), int(ut_act),
+                                                  L.act_beta(ut_act), int(per_sample), u1_w.data_ptr(), u1_b.data_ptr(),
+                                                  logits.data_ptr(), _ptr(bgfg), _ptr(tn), L.stream_ptr()),
+                "hier_combine_tn")
+        return logits, bgfg, tn
+    assert tfeat.coff == 0 and tfeat.cstride == tfeat.C and (tfeat.H, tfeat.W) == (2 * h, 2 * w)
     L.check(L.lib().hiseg_hier_combine_fwd(hdtype(tfeat.dtype), low.data_ptr(), N, h, w, tfeat.ptr(), tfeat.C,
                                            ut_w.data_ptr(), ut_scale.data_ptr(), ut_shift.data_ptr(), int(ut_act),
                                            L.act_beta(ut_act), int(per_sample), u1_w.data_ptr(), u1_b.data_ptr(), t_w.data_ptr(), t_b.data_ptr(),

@@ -155,8 +155,24 @@ typedef struct hiseg_conv2d_desc {
    * own; the call fails when the layer has no such kernel. */
   float* bnb_partial; const void* bnb_z; int bnb_z_cstride, bnb_z_coff;
   const float* bnb_scale; const float* bnb_shift; const float* bnb_mean; const float* bnb_invstd; int bnb_act;
+  /* Optional (round 7, inference head): per-pixel scale of source A -- px_scale f32 [N*H*W]; channel c of source
+   * pixel p is read as bf16(srcA[p][c] * px_scale[p]) (the spatial-attention multiply, attention_modules.py:113,
+   * fused into the loader of the ConvTranspose that alone consumes it; the same rounding as
+   * hiseg_pixel_scale_fwd, so the same bits).  Only the pointwise kernel's 256-channel ConvTranspose form has
+   * it: ask hiseg_conv2d_fused_ok first, the call fails where that returns 0. */
+  const float* px_scale;
+  /* Optional (round 7, inference head): a trailing 1x1 conv Cout -> 2 applied to the layer's bf16 output in
+   * the epilogue -- head2_out[p][k] = head2_b[k] + sum_c head2_w[k][c] * out[p][c] (f32, channels ascending, the
+   * arithmetic of hiseg_hier_combine_fwd's t_w / t_b) -- INSTEAD of storing the output (`out` may be NULL and
+   * is not written).  head2_w f32 [2][Cout], head2_b f32 [2], head2_out f32 [N*Ho*Wo][2].  Only the 3x3 halo
+   * kernel's 128-Cout residual form has it (hiseg_conv2d_fused_ok). */
+  const float* head2_w; const float* head2_b; float* head2_out;
 } hiseg_conv2d_desc;
 int hiseg_conv2d_fwd(const hiseg_conv2d_desc* d, hiseg_stream_t stream);
+/* 1 when hiseg_conv2d_fwd's automatic choice has a kernel that honours d->px_scale / d->head2_out for this
+ * layer (no launch); 0: the caller runs the separate passes (hiseg_pixel_scale_fwd before the conv; the conv,
+ * then hiseg_hier_combine_fwd on its output). */
+int hiseg_conv2d_fused_ok(const hiseg_conv2d_desc* d);
 /* sizeof of every descriptor struct of the C ABI, in the order roi_align_desc, conv2d_desc, wgrad_map, pack_entry,
  * bn_apply_desc, bn_bwd_desc, ln_bwd_desc, ew_view, ubf_desc, ubf_grads, loss_cfg, distill_cfg, roi_target_desc
  * (the first n of them into out); returns their count.  Bindings check their struct layouts against it. */
@@ -182,6 +198,12 @@ int hiseg_maxpool2x2_fwd(int dtype, const void* in, int N, int H, int W, int C, 
  * `stats` is caller workspace of N*H*W*2 floats, `att` of N*H*W floats. */
 int hiseg_attn_spatial_fwd(int dtype, const void* x, int N, int H, int W, int C, const float* w7,
                            int k, float* stats, float* att, void* out, hiseg_stream_t stream);
+/* The two halves of hiseg_attn_spatial_fwd: the attention map att [N*H*W] alone (the consumer then applies it
+ * while loading: hiseg_conv2d_desc.px_scale), and out = x * att[pixel]. */
+int hiseg_attn_map_fwd(int dtype, const void* x, int N, int H, int W, int C, const float* w7,
+                       int k, float* stats, float* att, hiseg_stream_t stream);
+int hiseg_pixel_scale_fwd(int dtype, const void* x, long long P, int C, const float* att, void* out,
+                          hiseg_stream_t stream);
 
 /* Global average pool + two 1x1 convs + sigmoid gate, shared by ChannelAttentionModule
  * (advanced/attention_modules.py:10-64: no bias, act = the module activation) and the
@@ -245,6 +267,12 @@ int hiseg_hier_combine_fwd(int dtype, const float* low, int N, int h, int w, con
                            int ut_act, float ut_beta, int ut_per_sample, const float* u1_w,
                            const float* u1_b, const float* t_w, const float* t_b, float* logits,
                            float* bgfg, float* tn, hiseg_stream_t stream);
+/* The same with the target branch's last 1x1 already applied by the producing conv's epilogue
+ * (hiseg_conv2d_desc.head2_out): tn2 f32 [N*2h*2w][2] in place of tfeat / t_w / t_b. */
+int hiseg_hier_combine_tn_fwd(const float* low, int N, int h, int w, const float* tn2, const float* ut_w,
+                              const float* ut_scale, const float* ut_shift, int ut_act, float ut_beta,
+                              int ut_per_sample, const float* u1_w, const float* u1_b, float* logits,
+                              float* bgfg, float* tn, hiseg_stream_t stream);
 /* upsample_bg_fg with LayerNorm2d (normalization_type 'layernorm2d', model.py:18-38): per-sample
  * statistics of z = ConvTranspose2d(low) (+ bias) over (32, 2h, 2w) -> mean/invstd [N] (optional)
  * and the folded tables scale/shift [N][32]: act(z * scale + shift) -- or, with fold_bias = 1, the
