@@ -77,8 +77,20 @@ __device__ __forceinline__ void hc_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned l
 // include/hiseg.h): the workgroup holds every output channel of its 256 pixels (Cout == BCO == 128), so after the
 // conversion barrier thread t reads tile row t from LDS and sums its 128 bf16 values against the two weight rows
 // (head2_acc, the loop of hier_combine_kernel) and stores 8 bytes; the 64-KiB bf16 tile never leaves the CU.
+// GA (round 8): source A gated per (image, channel) while it is loaded (d.a_gate, include/hiseg.h) -- the R3, ReLU,
+// no-residual form only.  The halo pieces come through registers instead of LDS-DMA: buffer_load_dwordx4 of the
+// lane's 8 channels, multiplied by the gate's 8 values of that channel octet (f32, rounded to bf16 as
+// channel_scale_kernel rounds), then one ds_write_b128 to the slot the DMA would have filled.  A lane always loads
+// channel octet lane % 4 of its halo row and applies the layout's slot swizzle to the LDS address (the DMA, whose
+// LDS address is lane-linear, applies it to the source address instead), so one pair of 16-B gate loads per block
+// serves every piece.  Pieces loaded after row PROW of a (slice, kx) block are written after row PROW of the NEXT
+// block (slice sl + 2's halves in blocks kx 1 and kx 2 of slice sl): a whole block for the loads to land, 12 staging
+// registers.  Every vector-memory load of this form is the compiler's to count (no asm DMA), so the hand-written
+// vmcnt waits of the ring are absent; the slice barrier's LDS wait covers the ds_writes.
+// RG (round 8): the residual gated per (image, output channel) in the H2 epilogue's conversion loop (d.res_gate):
+// bf16(residual * gate) before the add.
 template <int ACT, bool RES, int NW, bool UP = false, int ABL = 0, bool RP = false, bool ST = false, int TWB = 1,
-          bool BR = false, bool R3 = false, bool H2 = false>
+          bool BR = false, bool R3 = false, bool H2 = false, bool GA = false, bool RG = false>
 __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(ConvArgs a) {
   constexpr int NCG = NW / TWB;                      // Cout groups of 32
   constexpr int BCO = 32 * NCG, TM = 2, NR = 16;    // wave tile: 32 Cout x (16 rows x 16 columns)
@@ -93,6 +105,8 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
   static_assert((NW == 4 || NW == 8) && (TWB == 1 || (TWB == 2 && NW == 4 && !RP)), "configuration");
   static_assert(!R3 || (NW == 4 && !RP && TWB == 1 && !ST && !BR), "R3: the plain / residual 128-Cout form");
   static_assert(!H2 || (NW == 4 && TWB == 1 && !ST && !BR && !UP && !RP && ABL == 0), "H2: the 128-Cout one-block form");
+  static_assert(!GA || (R3 && !RES && !UP && !H2 && ABL == 0 && ACT == HISEG_ACT_RELU), "GA: the R3 ReLU form");
+  static_assert(!RG || (H2 && RES), "RG: the H2 residual form");
   // halo pieces the last wave issues per slice (the fewest of any wave): the vmcnt bound that still waits for every
   // piece of an older slice
   constexpr int NPMIN = ((NHR + 15) / 16 - 1 - (NW - 1)) / NW + 1;
@@ -166,7 +180,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
     const int hy = hr / HWD, hx = hr - HWD * hy;
     const int iy = y0 + hy - 1, ix = x0 + hx - 1;
     const bool ok = hr < NHR && (unsigned)iy < (unsigned)d.H && (unsigned)ix < (unsigned)d.W;
-    const int chunk = (ln & 3) ^ (((hx >> 2) & 1) << 1);
+    const int chunk = GA ? (ln & 3) : (ln & 3) ^ (((hx >> 2) & 1) << 1);   // (GA: the swizzle is in the LDS address)
     const bool fb = 32 * sl >= d.Ca;
     const int cs = fb ? d.b_cstride : d.a_cstride, coff = fb ? d.b_coff + 32 * sl - d.Ca : d.a_coff + 32 * sl;
     if constexpr (UP) {
@@ -189,6 +203,39 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
     const bool fb = 32 * sl >= d.Ca;
     const unsigned off = fb ? piece_off(p, sl) : pofA[p] + 64u * (unsigned)sl;
     hc_dma16(fb ? rB : rA, lds_base + (unsigned)(boff + 1024 * (NW * p + w)), off);
+  };
+  // GA: piece p's 16 B of slice sl into registers (an out-of-image lane reads zeros: its offset is past num_records)
+  auto halo_ld = [&](int p, int sl) __attribute__((always_inline)) -> hc_u4 {
+    if (16 * (NW * p + w) >= NHR) return hc_u4{0u, 0u, 0u, 0u};
+    return __builtin_amdgcn_raw_buffer_load_b128(rA, pofA[p] + 64u * (unsigned)sl, 0, 0);
+  };
+  // GA: bit p = the slot swizzle of piece p's halo column for this lane
+  unsigned gswz = 0;
+  if constexpr (GA) {
+#pragma unroll
+    for (int p = 0; p < PPW; ++p) {
+      const int hr = 16 * (NW * p + w) + (lane >> 2);
+      gswz |= (unsigned)(((hr % HWD) >> 2) & 1) << p;
+    }
+  }
+  // GA: the gate's 8 values of this lane's channel octet of slice sl (two 16-B loads)
+  const float* gate_l = GA ? d.a_gate + (long long)n * d.Ca + 8 * (lane & 3) : nullptr;
+  auto gate_ld = [&](floatx4 (&g)[2], int sl) __attribute__((always_inline)) {
+    g[0] = *reinterpret_cast<const floatx4*>(gate_l + 32 * sl);
+    g[1] = *reinterpret_cast<const floatx4*>(gate_l + 32 * sl + 4);
+  };
+  // GA: piece p gated, rounded and written to its place in the halo buffer at boff
+  auto halo_put = [&](int p, int boff, hc_u4 v, const floatx4 (&g)[2]) __attribute__((always_inline)) {
+    if (16 * (NW * p + w) >= NHR) return;
+    float f[8];
+    Chunk<bf16_t>::unpack(__builtin_bit_cast(uint4, v), f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[e] *= g[e >> 2][e & 3];
+    uint4 o = Chunk<bf16_t>::pack(f);
+    if ((int)pofA[p] < 0) o = make_uint4(0u, 0u, 0u, 0u);   // outside the image: zero whatever the gate holds
+    char* q = reinterpret_cast<char*>(smem) + boff + 1024 * (NW * p + w) +
+              ((lane << 4) ^ (int)(((gswz >> p) & 1u) << 5));
+    *reinterpret_cast<uint4*>(q) = o;
   };
   const char* lds_c = reinterpret_cast<const char*>(smem);
   // B fragment of halo row r at column shift kx: pixels (r, kx + lane % 16), channels 8 (lane / 16) .. + 7
@@ -247,16 +294,38 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
   }
   // ---- prologue: slice 0's halo, the weights of block (slice 0, kx 0)
   hc_u4 af[3][TM], an[3][TM];
+  hc_u4 pc[GA ? PH : 1];      // GA: the pieces in flight from one block to the next
+  floatx4 pg[2];              // GA: the gate values for the pieces a block writes
+  if constexpr (GA) {         // slices 0 and 1 through registers
+    hc_u4 p0[PPW], p1[PPW];
+    floatx4 g0[2], g1[2];
+    gate_ld(g0, 0);
 #pragma unroll
-  for (int p = 0; p < PPW; ++p) halo_dma(p, 0, hbuf(0));
-  if constexpr (R3) {
+    for (int p = 0; p < PPW; ++p) p0[p] = halo_ld(p, 0);
+    if (nsl > 1) {
+      gate_ld(g1, 1);
+#pragma unroll
+      for (int p = 0; p < PPW; ++p) p1[p] = halo_ld(p, 1);
+    }
+#pragma unroll
+    for (int p = 0; p < PPW; ++p) halo_put(p, hbuf(0), p0[p], g0);
     if (nsl > 1) {
 #pragma unroll
-      for (int p = 0; p < PPW; ++p) halo_dma(p, 1, hbuf(1));
+      for (int p = 0; p < PPW; ++p) halo_put(p, hbuf(1), p1[p], g1);
+    }
+  } else {
+#pragma unroll
+    for (int p = 0; p < PPW; ++p) halo_dma(p, 0, hbuf(0));
+    if constexpr (R3) {
+      if (nsl > 1) {
+#pragma unroll
+        for (int p = 0; p < PPW; ++p) halo_dma(p, 1, hbuf(1));
+      }
     }
   }
   load_blk(af, 0, 0);
-  if constexpr (R3) {   // slice 0's pieces (slice 1's, younger, may fly)
+  if constexpr (GA) {          // (the compiler waits for the pieces where halo_put reads them)
+  } else if constexpr (R3) {   // slice 0's pieces (slice 1's, younger, may fly)
     if (nsl > 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(6 + NPMIN) : "memory");
     else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
   } else {
@@ -271,7 +340,20 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
     constexpr int KX = decltype(kxc)::value;
     const int buf = hbuf(sl);
     const bool more = sl + 1 < nsl;
-    if ((ABL & 1) == 0 && (KX < 2 || more)) load_blk(an, KX < 2 ? sl : sl + 1, KX < 2 ? KX + 1 : 0);
+    // GA: the next block's weights are loaded after the pieces' turn at row PROW instead of here -- their 24 registers
+    // and the gating's temporaries (the gate, the unpacked values) are then never live together, which keeps the
+    // K loop free of spills (a spilled piece offset is reloaded through scratch, and that reload's vmcnt(0) waits for
+    // every weight load in flight)
+    auto next_weights = [&]() __attribute__((always_inline)) {
+      if ((ABL & 1) == 0 && (KX < 2 || more)) load_blk(an, KX < 2 ? sl : sl + 1, KX < 2 ? KX + 1 : 0);
+    };
+    if constexpr (GA) {
+      if constexpr (KX > 0) {
+        if (sl + 2 < nsl) gate_ld(pg, sl + 2);
+      }
+    } else {
+      next_weights();
+    }
     // This block's LDS-DMA pieces (the next slice's halo; RP: residual rows), issued after row 2's MFMAs.  The
     // compiler does not see the asm DMA in its vmcnt accounting, so a piece issued before its wait for a weight
     // fragment of this block would make that wait cover the weight loads issued at the start of this block (measured:
@@ -279,6 +361,18 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
     // this block to land (they are older than the next block's weight loads).
     auto pieces = [&]() __attribute__((always_inline)) {
       if constexpr ((ABL & 2) != 0) {
+      } else if constexpr (GA) {   // slice sl + 2's halo: write the pieces the previous block loaded, load the next
+        if (sl + 2 < nsl) {
+          if constexpr (KX > 0) {
+#pragma unroll
+            for (int p = (KX - 1) * PH; p < (KX == 1 ? PH : PPW); ++p)
+              halo_put(p, hbuf(sl + 2), pc[p - (KX - 1) * PH], pg);
+          }
+          if constexpr (KX < 2) {
+#pragma unroll
+            for (int p = KX * PH; p < (KX == 0 ? PH : PPW); ++p) pc[p - KX * PH] = halo_ld(p, sl + 2);
+          }
+        }
       } else if constexpr (R3 && KX < 2) {   // slice sl + 2's halo into the third buffer
         if (sl + 2 < nsl) {
 #pragma unroll
@@ -315,6 +409,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
       if (r == PROW) {
         __builtin_amdgcn_s_setprio(0);
         pieces();
+        if constexpr (GA) next_weights();
         __builtin_amdgcn_s_setprio(1);
       }
       if ((ABL & 4) == 0 && r + 2 < NR + 2) bq[(r + 2) % 3] = rdB(ln, buf, KX, r + 2);
@@ -339,7 +434,8 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
     }
     __builtin_amdgcn_s_setprio(0);
     if constexpr (KX == 2 && (ABL & 8) == 0) {
-      if constexpr (R3) {
+      if constexpr (GA) {   // no DMA in flight; the barrier's LDS wait covers the ds_writes
+      } else if constexpr (R3) {
         // slice sl + 1's pieces were issued during slice sl - 1: older than this slice's 18 weight loads and its
         // slice-(sl + 2) pieces, which may fly
         if (sl + 2 < nsl) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(18 + NPMIN) : "memory");
@@ -410,13 +506,14 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
                     : make_uint4(0u, 0u, 0u, 0u);
     }
   }
-  floatx4 sc[TM], sh[TM];
+  floatx4 sc[TM], sh[TM], rg[RG ? TM : 1];
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
     const int cl = wc * 32 + i * 16 + (lane >> 4) * 4;
     const int cc = co0 + cl < d.Cout ? co0 + cl : 0;
     sc[i] = *reinterpret_cast<const floatx4*>(d.scale + cc);
     sh[i] = *reinterpret_cast<const floatx4*>(d.shift + cc);
+    if constexpr (RG) rg[i] = *reinterpret_cast<const floatx4*>(d.res_gate + (long long)n * d.Cout + cc);
   }
   // accumulator rows j0 .. j1 - 1 (tile rows 16 j + lane % 16) -> bf16 output quads in place
   auto convert = [&](auto j0c, auto j1c) __attribute__((always_inline)) {
@@ -432,6 +529,11 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
         float v[4];
         uint2 rv = make_uint2(0u, 0u);
         if constexpr (RES) rv = *reinterpret_cast<const uint2*>(q);
+        if constexpr (RG) {   // bf16(residual * gate): channel_scale_kernel's arithmetic and rounding
+          const floatx4 gq = rg[RG ? i : 0];
+          rv = make_uint2(f2bf2(Quad<bf16_t>::get(rv, 0) * gq[0], Quad<bf16_t>::get(rv, 1) * gq[1]),
+                          f2bf2(Quad<bf16_t>::get(rv, 2) * gq[2], Quad<bf16_t>::get(rv, 3) * gq[3]));
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           v[e] = ac[e] * sc[i][e] + sh[i][e];
@@ -609,7 +711,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
 }
 
 template <int ACT, bool RES, int NW, bool UP = false, int ABL = 0, bool RP = false, bool ST = false, int TWB = 1,
-          bool BR = false, bool R3 = false, bool H2 = false>
+          bool BR = false, bool R3 = false, bool H2 = false, bool GA = false, bool RG = false>
 static int launch_hwc(const ConvArgs& a, hipStream_t s) {
   const hiseg_conv2d_desc& d = a.d;
   constexpr int BCO = 32 * NW / TWB, TW = 16 * TWB;
@@ -619,7 +721,7 @@ static int launch_hwc(const ConvArgs& a, hipStream_t s) {
   const int nco = d.Cout_pad / BCO;
   const size_t halo = R3 ? halo2 / 2 * 3 : halo2;
   const size_t lds = RP ? (size_t)80 * 1024 : (halo > epi ? halo : epi);
-  auto kern = conv_hwc_kernel<ACT, RES, NW, UP, ABL, RP, ST, TWB, BR, R3, H2>;
+  auto kern = conv_hwc_kernel<ACT, RES, NW, UP, ABL, RP, ST, TWB, BR, R3, H2, GA, RG>;
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1013,12 +1115,22 @@ static bool conv_hwc_applies(const ConvArgs& a, int variant) {
       ((variant != 104 && variant != 108) || d.Cout != 128 || !d.residual || d.a_up != 1 || d.stats_partial ||
        d.bnb_partial || !d.head2_w || !d.head2_b || ((uintptr_t)d.head2_out & 7)))
     return false;
+  // the channel gates (GA / RG) exist in variant 108 alone: source A's in its ReLU, no-residual, single-source form,
+  // the residual's beside the trailing 1x1
+  if (d.a_gate &&
+      (variant != 108 || d.residual || d.act != HISEG_ACT_RELU || d.a_up != 1 || d.Cb || d.stats_partial ||
+       d.bnb_partial || d.head2_out || d.res_gate || ((uintptr_t)d.a_gate & 15)))
+    return false;
+  if (d.res_gate && (variant != 108 || !d.head2_out || !d.residual || ((uintptr_t)d.res_gate & 15))) return false;
   return true;
 }
 
-// Whether the automatic choice's variant (r3: 108, else 104) takes the layer with its head2 epilogue.
-bool conv_hwc_head2_applies(const ConvArgs& a, bool r3) {
-  return a.d.head2_out != nullptr && conv_hwc_applies(a, r3 ? 108 : 104);
+// The variant with which the automatic choice (r3: 108, else 104) takes the layer with its fused operands -- the
+// head2 epilogue, the channel gates (variant 108 alone) -- or 0 when it has no such form.
+int conv_hwc_fused_variant(const ConvArgs& a, bool r3) {
+  if (!a.d.head2_out && !a.d.a_gate) return 0;
+  const int v = r3 ? 108 : 104;
+  return conv_hwc_applies(a, v) ? v : 0;
 }
 
 // BatchNorm statistics partials the automatic choice would fuse into this layer's epilogue (0: none): the pixel tiles
@@ -1038,6 +1150,10 @@ int conv_hwc_stats_tiles(const ConvArgs& a) {
 int conv_hwc_try(const ConvArgs& a, hipStream_t s, int variant) {
   const hiseg_conv2d_desc& d = a.d;
 #ifdef HISEG_DIAG
+  if (variant == 148) {   // variant 108's gated-source form by number (tools/conv_bench.py times it beside 108)
+    if (!d.a_gate) return 0;
+    variant = 108;
+  }
   if (variant >= 150 && variant < 4300) {   // timing ablations of variant 104 (res + ReLU only; output buffer as
                                           // scratch: the ABL 32 store writes one float per thread and MFMA row)
     if (d.weight_frag == nullptr || !d.residual || d.act != HISEG_ACT_RELU || d.a_up != 1 || d.Cout % 128) return 0;
@@ -1078,6 +1194,16 @@ int conv_hwc_try(const ConvArgs& a, hipStream_t s, int variant) {
     else
       r = d.a_up == 2 ? launch_hwc<HISEG_ACT_NONE, false, 4, true, 0, false, true>(a, s)
                       : launch_hwc<HISEG_ACT_NONE, false, 4, false, 0, false, true>(a, s);
+    return r < 0 ? r : 1;
+  }
+  if (d.a_gate) {   // the gated source A (variant 108, ReLU, no residual; conv_hwc_applies checked the form)
+    const int r = launch_hwc<HISEG_ACT_RELU, false, 4, false, 0, false, false, 1, false, true, false, true>(a, s);
+    return r < 0 ? r : 1;
+  }
+  if (d.head2_out && d.res_gate) {   // the trailing-1x1 epilogue with the gated residual (variant 108)
+    const int r = d.act == HISEG_ACT_RELU
+                      ? launch_hwc<HISEG_ACT_RELU, true, 4, false, 0, false, false, 1, false, true, true, false, true>(a, s)
+                      : launch_hwc<HISEG_ACT_NONE, true, 4, false, 0, false, false, 1, false, true, true, false, true>(a, s);
     return r < 0 ? r : 1;
   }
   if (d.head2_out) {   // the trailing-1x1 epilogue (variants 104 / 108, residual; conv_hwc_applies checked the form)

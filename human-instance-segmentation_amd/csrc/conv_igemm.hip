@@ -502,7 +502,7 @@ int conv_hwr_try(const ConvArgs& a, hipStream_t s, int variant);
 int conv_hwt_try(const ConvArgs& a, hipStream_t s, int variant);
 int conv_hwc_try(const ConvArgs& a, hipStream_t s, int variant);
 int conv_hwc_stats_tiles(const ConvArgs& a);
-bool conv_hwc_head2_applies(const ConvArgs& a, bool r3);
+int conv_hwc_fused_variant(const ConvArgs& a, bool r3);
 int conv_small_try(const ConvArgs& a, hipStream_t s, int variant);
 int conv_rows_try(const ConvArgs& a, hipStream_t s, int variant);
 bool conv_pw_applies(const ConvArgs& a);
@@ -584,9 +584,21 @@ extern "C" int hiseg_conv2d_stats_tiles(const hiseg_conv2d_desc* d) {
   return conv_hwc_stats_tiles(a);
 }
 
+// The fused operands of rounds 7 and 8 -- whether any is set, and in a combination some kernel has: px_scale alone
+// (the pointwise kernel); head2_out, with or without res_gate; a_gate alone (the 3x3 halo kernel).
+static bool has_fused_operands(const hiseg_conv2d_desc* d) {
+  return d->px_scale || d->head2_out || d->a_gate || d->res_gate;
+}
+static bool fused_operands_ok(const hiseg_conv2d_desc* d) {
+  if (!has_fused_operands(d)) return false;
+  if (d->px_scale) return !d->head2_out && !d->a_gate && !d->res_gate;
+  if (d->a_gate) return !d->head2_out && !d->res_gate;
+  return d->head2_out != nullptr;   // (res_gate rides with head2_out only)
+}
+
 extern "C" int hiseg_conv2d_fused_ok(const hiseg_conv2d_desc* d) {
-  if (d == nullptr || d->dtype != HISEG_BF16 || d->N <= 0 || (!d->px_scale && !d->head2_out) ||
-      (d->px_scale && d->head2_out) || d->stats_partial || d->bnb_partial || d->a_up != 1 || d->K_pad % 64)
+  if (d == nullptr || d->dtype != HISEG_BF16 || d->N <= 0 || !fused_operands_ok(d) || d->stats_partial ||
+      d->bnb_partial || d->a_up != 1 || d->K_pad % 64)
     return 0;
   const long long M = (long long)d->N * d->Ho * d->Wo;
   if (M >= (1ll << 31)) return 0;
@@ -597,7 +609,7 @@ extern "C" int hiseg_conv2d_fused_ok(const hiseg_conv2d_desc* d) {
   a.nK = d->K_pad / 64;
   a.Hs = d->H;
   a.Ws = d->W;
-  return d->px_scale ? (conv_pw_applies(a) ? 1 : 0) : (conv_hwc_head2_applies(a, hwc_r3_mode()) ? 1 : 0);
+  return d->px_scale ? (conv_pw_applies(a) ? 1 : 0) : (conv_hwc_fused_variant(a, hwc_r3_mode()) ? 1 : 0);
 }
 
 extern "C" int hiseg_conv2d_fwd_variant(const hiseg_conv2d_desc* d, int variant, hiseg_stream_t stream) {
@@ -614,9 +626,16 @@ static int conv2d_impl(const hiseg_conv2d_desc* d, hiseg_stream_t stream, int va
   HISEG_REQUIRE(d->out_dtype == HISEG_F32 || d->out_dtype == HISEG_BF16, HISEG_ERR_BAD_DTYPE, "conv2d: out_dtype %d", d->out_dtype);
   HISEG_REQUIRE(d->srcA && d->weight && d->scale && d->shift && (d->out || d->head2_out), HISEG_ERR_BAD_ARG,
                 "conv2d: null pointer");
-  HISEG_REQUIRE(!(d->px_scale || d->head2_out) || (variant == 0 && !d->stats_partial && !d->bnb_partial &&
-                                                   !(d->px_scale && d->head2_out)),
-                HISEG_ERR_BAD_ARG, "conv2d: px_scale / head2_out go with the automatic choice alone, one at a time");
+#ifdef HISEG_DIAG
+  const bool fused_variant = variant == 0 || (variant == 148 && d->a_gate);   // (148: the gated form, for timing)
+#else
+  const bool fused_variant = variant == 0;
+#endif
+  HISEG_REQUIRE(!has_fused_operands(d) ||
+                    (fused_variant && !d->stats_partial && !d->bnb_partial && fused_operands_ok(d)),
+                HISEG_ERR_BAD_ARG,
+                "conv2d: px_scale / head2_out / a_gate / res_gate go with the automatic choice alone: px_scale or "
+                "a_gate by itself, res_gate only beside head2_out");
   HISEG_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ho > 0 && d->Wo > 0, HISEG_ERR_BAD_SHAPE, "conv2d: empty grid");
   HISEG_REQUIRE(d->KH > 0 && d->KW > 0 && d->stride > 0 && d->pad >= 0, HISEG_ERR_BAD_SHAPE, "conv2d: bad window");
   HISEG_REQUIRE(d->a_up == 1 || d->a_up == 2, HISEG_ERR_BAD_SHAPE, "conv2d: a_up must be 1 or 2");
@@ -704,6 +723,8 @@ static int conv2d_impl(const hiseg_conv2d_desc* d, hiseg_stream_t stream, int va
         if (d->in_scale) c.in_scale = d->in_scale + (long long)n0 * d->Ca;   // per-image SE gate [N][Ca]
         if (d->px_scale) c.px_scale = d->px_scale + n0 * in_px;              // per-pixel scale of source A
         if (d->head2_out) c.head2_out = d->head2_out + 2 * n0 * out_px;      // [pixels][2]
+        if (d->a_gate) c.a_gate = d->a_gate + (long long)n0 * d->Ca;         // per-image channel gates [N][Ca]
+        if (d->res_gate) c.res_gate = d->res_gate + (long long)n0 * d->Cout;   // [N][Cout]
         const int r = conv2d_impl(&c, stream, variant);
         if (r) return r;
       }
@@ -727,10 +748,12 @@ static int conv2d_impl(const hiseg_conv2d_desc* d, hiseg_stream_t stream, int va
   a.kper = a.nK;
   // The fused operands of round 7 exist in one kernel each, and no other kernel may take the layer and silently
   // ignore them: the caller asks hiseg_conv2d_fused_ok first.
-  if (d->px_scale || d->head2_out) {
-    const int r = d->px_scale ? conv_pw_try(a, s, 90) : conv_hwc_try(a, s, hwc_r3_mode() ? 108 : 104);
+  if (has_fused_operands(d)) {
+    const int r = d->px_scale ? conv_pw_try(a, s, 90)
+                              : conv_hwc_try(a, s, variant ? variant : hwc_r3_mode() ? 108 : 104);
     HISEG_REQUIRE(r != 0, HISEG_ERR_BAD_ARG,
-                  "conv2d: no kernel takes this layer with px_scale / head2_out (hiseg_conv2d_fused_ok)");
+                  "conv2d: no kernel takes this layer with px_scale / head2_out / a_gate / res_gate "
+                  "(hiseg_conv2d_fused_ok)");
     return r < 0 ? r : HISEG_OK;
   }
   if (variant == 99 || variant == 0) {

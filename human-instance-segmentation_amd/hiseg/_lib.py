@@ -144,6 +144,7 @@ class Conv2dDesc(Desc):
         ("bnb_act", c_int),
         ("px_scale", c_void_p),
         ("head2_w", c_void_p), ("head2_b", c_void_p), ("head2_out", c_void_p),
+        ("a_gate", c_void_p), ("res_gate", c_void_p),
     ]
 
 

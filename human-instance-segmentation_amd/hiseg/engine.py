@@ -160,12 +160,35 @@ def _check_input(x: torch.Tensor, what: str):
 
 
 # ------------------------------------------------------------------------------------ blocks
+def _block_acts(blk: nn.Module) -> Tuple[int, int]:
+    return (act_code(blk.activation1 if hasattr(blk, "activation1") else blk.activation),
+            act_code(blk.activation2 if hasattr(blk, "activation2") else blk.activation))
+
+
+def gated_block_ok(E: Ctx, blk: nn.Module, x: Act, gate: torch.Tensor, head2: ops.Head2) -> bool:
+    """Whether both convs of a ResidualBlock whose input is x * gate[image][channel] (and whose output feeds only
+    ``head2``) apply the gate where they read x -- conv1 in its loader, conv2 on its residual.  All or nothing: if
+    either conv lacks the form the gated tensor has to exist anyway."""
+    if isinstance(blk.norm1, LayerNorm2d) or isinstance(blk.norm2, LayerNorm2d) or x.dtype != torch.bfloat16:
+        return False
+    a1, a2 = _block_acts(blk)
+    p1, p2 = E.conv(blk.conv1, blk.norm1, a1), E.conv(blk.conv2, blk.norm2, a2)
+    if p1.cout != x.C or p2.cout != x.C:   # (conv2's input is conv1's output: x stands in for its shape below)
+        return False
+    return ops._fused_ok(p1, x, None, None, None, None, None, None, x.dtype, 1, a_gate=gate) and \
+        ops._fused_ok(p2, x, None, x, None, None, None, head2, x.dtype, 1, res_gate=gate)
+
+
 def residual_block(E: Ctx, blk: nn.Module, x: Act, out: Optional[Act] = None,
-                   head2: Optional[ops.Head2] = None) -> Optional[Act]:
+                   head2: Optional[ops.Head2] = None, in_gate: Optional[torch.Tensor] = None) -> Optional[Act]:
     """ResidualBlock (refinement.py:31-55 / unet.py:35-58): two fused launches.  ``head2``: a 1x1 -> 2 that alone
-    consumes the block's output (ops.Head2); returns None when conv2's epilogue applied it."""
-    a1 = act_code(blk.activation1 if hasattr(blk, "activation1") else blk.activation)
-    a2 = act_code(blk.activation2 if hasattr(blk, "activation2") else blk.activation)
+    consumes the block's output (ops.Head2); returns None when conv2's epilogue applied it.  ``in_gate`` (f32
+    [N, C]): the block's input is x * in_gate[image][channel], applied by both convs as they read x (the caller
+    checked gated_block_ok)."""
+    a1, a2 = _block_acts(blk)
+    if in_gate is not None:
+        h = ops.conv2d(E.conv(blk.conv1, blk.norm1, a1), x, a_gate=in_gate)
+        return ops.conv2d(E.conv(blk.conv2, blk.norm2, a2), h, residual=x, res_gate=in_gate, head2=head2)
     h = cna(E, blk.conv1, blk.norm1, a1, x)
     if head2 is not None and out is None and not isinstance(blk.norm2, LayerNorm2d):
         return ops.conv2d(E.conv(blk.conv2, blk.norm2, a2), h, residual=x, head2=head2)
@@ -255,17 +278,21 @@ def hier_head(E: Ctx, head: nn.Module, feat: Act, aux: str) -> Tuple[torch.Tenso
         gate = ops.se_gate(t, E.f32(ca.fc1.weight, (ca.fc1.out_channels, ca.fc1.in_channels)), None,
                            E.f32(ca.fc2.weight, (ca.fc2.out_channels, ca.fc2.in_channels)), None,
                            act_code(ca.activation))
-        t = ops.channel_scale(t, gate)
         blk, last = tb[8], tb[9]
     else:
         t = residual_block(E, tb[0], gated)
         t = cna(E, tb[2], tb[3], act_code(tb[4]), t, convT=True)
         blk, last = tb[6], tb[7]
+        gate = None
     # the branch's last residual block feeds only its last 1x1 (-> 2), which rides in conv2's epilogue where the
     # layer has that form (ops.Head2): t is then None and h2.out the two target logits per pixel
     h2 = ops.Head2(E.f32(last.weight, (2, last.in_channels)), E.f32(last.bias))
+    # the channel-attention multiply (attention_modules.py:64) rides in the two convs that alone read its result
+    # where both have that form; otherwise the gated tensor is written by its own pass
+    if gate is not None and not gated_block_ok(E, blk, t, gate, h2):
+        t, gate = ops.channel_scale(t, gate), None
     tH, tW = t.H, t.W
-    t = residual_block(E, blk, t, head2=h2)
+    t = residual_block(E, blk, t, head2=h2, in_gate=gate)
     mh, mw = bh.mask_height, bh.mask_width
     if (tH, tW) != (mh, mw) or (2 * low.H, 2 * low.W) != (mh, mw):
         raise NotImplementedError(f"mask size {mh}x{mw} must be 2x the ROI size {low.H}x{low.W} on the hiseg path")

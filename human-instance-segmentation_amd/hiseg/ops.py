@@ -290,9 +290,14 @@ def conv2d(p: ConvPlan, xa: Act, xb: Optional[Act] = None, out: Optional[Act] = 
            residual: Optional[Act] = None, mul: Optional[Act] = None, out2: Optional[Act] = None,
            in_scale: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None,
            variant: int = 0, out_cpad: Optional[int] = None, split_k_3x3: bool = False,
-           px_scale: Optional[torch.Tensor] = None, head2: Optional[Head2] = None) -> Optional[Act]:
+           px_scale: Optional[torch.Tensor] = None, head2: Optional[Head2] = None,
+           a_gate: Optional[torch.Tensor] = None, res_gate: Optional[torch.Tensor] = None) -> Optional[Act]:
     """hiseg_conv2d_fwd.  Returns the output Act (allocated when ``out`` is None; ``out_cpad``: its channel
     stride, the pad channels zero).
+
+    ``a_gate`` (f32 [N, Ca]) / ``res_gate`` (f32 [N, Cout]): source A / the residual is read as
+    bf16(x * gate[image][channel]) -- inside the kernel where the layer has that form (hiseg_conv2d_fused_ok; the
+    residual's only beside ``head2``), through a channel_scale pass otherwise; the same bits either way.
 
     ``px_scale`` (f32, one value per source pixel): source A is read as bf16(xa * px_scale[pixel]) -- inside the
     kernel's loader where the layer has that form (hiseg_conv2d_fused_ok), through a pixel_scale pass otherwise; the
@@ -313,10 +318,23 @@ def conv2d(p: ConvPlan, xa: Act, xb: Optional[Act] = None, out: Optional[Act] = 
         Ho = (H + 2 * p.pad - p.kh) // p.stride + 1
         Wo = (W + 2 * p.pad - p.kw) // p.stride + 1
         oH, oW = Ho, Wo
+    if a_gate is not None:
+        assert px_scale is None and head2 is None and res_gate is None
+        if variant or out2 is not None or not _fused_ok(p, xa, xb, residual, mul, in_scale, None, None,
+                                                        out_dtype or dt, a_up, a_gate=a_gate):
+            xa, a_gate = channel_scale(xa, a_gate), None
+    if res_gate is not None:
+        assert residual is not None
+        if head2 is None or variant or out is not None or out2 is not None or \
+                not _fused_ok(p, xa, xb, residual, mul, in_scale, None, head2, out_dtype or dt, a_up,
+                              res_gate=res_gate):
+            residual, res_gate = channel_scale(residual, res_gate), None
     fused = (px_scale is not None or head2 is not None) and not variant and out is None and out2 is None
     if fused:
         assert px_scale is None or head2 is None
-        fused = _fused_ok(p, xa, xb, residual, mul, in_scale, px_scale, head2, out_dtype or dt, a_up)
+        fused = _fused_ok(p, xa, xb, residual, mul, in_scale, px_scale, head2, out_dtype or dt, a_up,
+                          res_gate=res_gate)
+    assert res_gate is None or fused
     if px_scale is not None and not fused:
         xa = pixel_scale(xa, px_scale)
     if head2 is not None:
@@ -349,6 +367,10 @@ def conv2d(p: ConvPlan, xa: Act, xb: Optional[Act] = None, out: Optional[Act] = 
         d.head2_w, d.head2_b, d.head2_out = head2.w, head2.b, head2.out
     if fused and px_scale is not None:
         d.px_scale = px_scale
+    if a_gate is not None:
+        d.a_gate = a_gate
+    if res_gate is not None:
+        d.res_gate = res_gate
     if out2 is not None:
         assert out2.dtype == dt
         d.out2, d.o2_cstride, d.o2_coff = out2, out2.cstride, out2.coff
@@ -368,7 +390,7 @@ def conv2d(p: ConvPlan, xa: Act, xb: Optional[Act] = None, out: Optional[Act] = 
             d.workspace, d.workspace_bytes = ws, nbytes
     if RECORD is not None:
         dc = d.copy()
-        keep = [t for t in (xa, xb, out, residual, mul, out2, ws, px_scale) if t is not None]
+        keep = [t for t in (xa, xb, out, residual, mul, out2, ws, px_scale, a_gate, res_gate) if t is not None]
         flops = 2.0 * d.N * d.Ho * d.Wo * p.gemm_cols * p.kh * p.kw * (xa.C + (xb.C if xb is not None else 0))
         RECORD.append((dc, keep, p, flops))
     gate = GATE
@@ -384,10 +406,17 @@ def conv2d(p: ConvPlan, xa: Act, xb: Optional[Act] = None, out: Optional[Act] = 
     return out
 
 
-def _fused_ok(p, xa, xb, residual, mul, in_scale, px_scale, head2, out_dtype, a_up) -> bool:
-    """Whether the library has a kernel that applies px_scale / head2 inside this layer (planning only, no launch)."""
+def _fused_ok(p, xa, xb, residual, mul, in_scale, px_scale, head2, out_dtype, a_up, a_gate=None, res_gate=None) -> bool:
+    """Whether the library has a kernel that applies px_scale / head2 / a_gate / res_gate (all that are given) inside
+    this layer (planning only, no launch)."""
     if xa.dtype != torch.bfloat16 or out_dtype != torch.bfloat16 or xb is not None or mul is not None or \
             in_scale is not None or a_up != 1:
+        return False
+    for gt, c in ((a_gate, p.ca), (res_gate, p.cout)):
+        if gt is not None:
+            assert gt.dtype == torch.float32 and gt.is_contiguous() and tuple(gt.shape) == (xa.N, c), \
+                (gt.dtype, tuple(gt.shape), (xa.N, c))
+    if a_gate is not None and xa.C != p.ca:
         return False
     if px_scale is not None:
         assert px_scale.dtype == torch.float32 and px_scale.is_contiguous() and px_scale.numel() == xa.N * xa.H * xa.W
@@ -419,6 +448,11 @@ def _fused_ok(p, xa, xb, residual, mul, in_scale, px_scale, head2, out_dtype, a_
         d.out = xa   # (any aligned address: the plan looks at the output's alignment only)
     if head2 is not None:
         d.head2_w, d.head2_b, d.head2_out = head2.w, head2.b, head2.w
+    if a_gate is not None:
+        d.a_gate = a_gate
+        d.out = xa
+    if res_gate is not None:
+        d.res_gate = res_gate
     return bool(L.lib().hiseg_conv2d_fused_ok(ctypes.byref(d)))
 
 

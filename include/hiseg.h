@@ -167,11 +167,22 @@ typedef struct hiseg_conv2d_desc {
    * is not written).  head2_w f32 [2][Cout], head2_b f32 [2], head2_out f32 [N*Ho*Wo][2].  Only the 3x3 halo
    * kernel's 128-Cout residual form has it (hiseg_conv2d_fused_ok). */
   const float* head2_w; const float* head2_b; float* head2_out;
+  /* Optional (round 8, inference head): per-image channel gates applied where the layer reads a tensor, in place
+   * of a hiseg_channel_scale_fwd pass over it (ChannelAttentionModule's x * gate, attention_modules.py:64; the same
+   * rounding -- unpack to f32, multiply, round to bf16 -- so the same bits).
+   *   a_gate   f32 [N][Ca]:   channel c of source A of image n is read as bf16(srcA * a_gate[n][c]); out-of-image
+   *                           halo pixels stay zero.  Only the 3x3 halo kernel's 128-Cout ring-of-three form with
+   *                           ReLU and no residual, single source.
+   *   res_gate f32 [N][Cout]: the residual is read as bf16(residual * res_gate[n][co]) before it is added.  Only
+   *                           together with head2_out (the 128-Cout residual form above).
+   * Both tables 16-B aligned.  Ask hiseg_conv2d_fused_ok first, the call fails where that returns 0. */
+  const float* a_gate; const float* res_gate;
 } hiseg_conv2d_desc;
 int hiseg_conv2d_fwd(const hiseg_conv2d_desc* d, hiseg_stream_t stream);
-/* 1 when hiseg_conv2d_fwd's automatic choice has a kernel that honours d->px_scale / d->head2_out for this
- * layer (no launch); 0: the caller runs the separate passes (hiseg_pixel_scale_fwd before the conv; the conv,
- * then hiseg_hier_combine_fwd on its output). */
+/* 1 when hiseg_conv2d_fwd's automatic choice has a kernel that honours d->px_scale / d->head2_out / d->a_gate /
+ * d->res_gate (every one of them that is set) for this layer (no launch); 0: the caller runs the separate passes
+ * (hiseg_pixel_scale_fwd / hiseg_channel_scale_fwd before the conv; the conv, then hiseg_hier_combine_fwd on its
+ * output). */
 int hiseg_conv2d_fused_ok(const hiseg_conv2d_desc* d);
 /* sizeof of every descriptor struct of the C ABI, in the order roi_align_desc, conv2d_desc, wgrad_map, pack_entry,
  * bn_apply_desc, bn_bwd_desc, ln_bwd_desc, ew_view, ubf_desc, ubf_grads, loss_cfg, distill_cfg, roi_target_desc
