@@ -489,3 +489,190 @@ extern "C" int hiseg_bilateral_fwd(const float* x, float* out, long long NC, int
 #undef HISEG_BL
   return hiseg_check_launch("bilateral");
 }
+
+// ---- EdgePreservingFilter (bilateral_filter.py:219-296): the guided filter
+//
+// out = box(a)*g + box(b), a = (box(x*g) - box(x)*box(g)) / (box(g*g) - box(g)^2 + eps), b = box(x) - a*box(g); box is
+// the zero-padded k x k sum (k = 2r+1) divided by k*k.  One workgroup owns a tile of one output plane.  The inputs
+// live in LDS on a halo of 2R around the tile, a and b on a halo of R; R = r in the tiled form and 0 in the
+// resident form (the tile is the plane, and a tap outside it is the zero padding).  Every box is separable: row sums
+// first, then column sums, each a plain f32 sum over dx (dy) = -r..r in that order.  A tap that is skipped because
+// it lies outside the plane would have added an exact zero, so a pixel sees the same additions in the same order
+// wherever its tile lies: both forms give the same bits.  a and b are zero outside the image, as the reference's
+// second convolution pads them, also where their own window overlaps the image.
+//
+// LDS: x and g over the input region, two row-sum planes (input rows x a/b columns), two a/b-domain planes: six
+// f32 planes in the resident form, kGuidedResidentPx = 160 KB / 24 B pixels.  The four first-stage boxes go through
+// the two row-sum planes in two rounds (x and g, then x*g and g*g).
+
+namespace hiseg {
+
+constexpr int kGuidedResidentPx = kPostLds / 24;
+constexpr int kGuidedMaxRadius = kMaxHalo / 2;
+
+struct GuidedGeom {
+  int H, W;            // plane
+  int TH, TW;          // tile
+  int tiles_x, tiles;  // tiles per row / per plane
+  int R;               // halo of a and b around the tile; the inputs carry 2R
+  int Cx, Cg, Co;      // channels of x, of the guide and of out (the broadcast of the two)
+};
+
+// d1[row][c] = sum over dx = -r..r of s1[row][c + off + dx] (d2 of s2 likewise), rows x DW from rows x SW; PROD:
+// of s1*s2 and s2*s2.  Taps outside the source row are zero padding and add nothing.
+template <bool PROD>
+__device__ __forceinline__ void row_sums(const float* s1, const float* s2, float* d1, float* d2, int rows, int SW,
+                                         int DW, int off, int r) {
+  for (int i = threadIdx.x; i < rows * DW; i += blockDim.x) {
+    const int row = i / DW, c = i - row * DW;
+    const int lo = max(c + off - r, 0), hi = min(c + off + r, SW - 1);
+    const float* p1 = s1 + row * SW;
+    const float* p2 = s2 + row * SW;
+    float u = 0.f, v = 0.f;
+    for (int k = lo; k <= hi; ++k) {
+      const float e1 = p1[k], e2 = p2[k];
+      if constexpr (PROD) {
+        u = fmaf(e1, e2, u);
+        v = fmaf(e2, e2, v);
+      } else {
+        u += e1;
+        v += e2;
+      }
+    }
+    d1[i] = u;
+    d2[i] = v;
+  }
+  __syncthreads();
+}
+
+// Sum over dy = -r..r of s[row + dy][col] in a plane of SH x SW; rows outside it are zero padding.
+__device__ __forceinline__ float col_sum(const float* s, int SH, int SW, int row, int col, int r) {
+  const int lo = max(row - r, 0), hi = min(row + r, SH - 1);
+  float u = 0.f;
+  for (int k = lo; k <= hi; ++k) u += s[k * SW + col];
+  return u;
+}
+
+__global__ void __launch_bounds__(1024) guided_filter_kernel(const float* __restrict__ x, const float* __restrict__ guide,
+                                                             float* __restrict__ out, GuidedGeom q, int r, float eps) {
+  extern __shared__ float post_lds[];
+  const long long plane = blockIdx.x / q.tiles;
+  const int tile = (int)(blockIdx.x % q.tiles);
+  const int ty0 = (tile / q.tiles_x) * q.TH, tx0 = (tile % q.tiles_x) * q.TW;
+  const int RH = q.TH + 4 * q.R, RW = q.TW + 4 * q.R;   // input region
+  const int AH = q.TH + 2 * q.R, AW = q.TW + 2 * q.R;   // a / b domain
+  const long long HW = (long long)q.H * q.W;
+  const float kk = (float)((2 * r + 1) * (2 * r + 1));
+  float* X = post_lds;
+  float* G = X + RH * RW;
+  float* h1 = G + RH * RW;      // row sums: RH x AW (the last stage uses AH x TW of it)
+  float* h2 = h1 + RH * AW;
+  float* m1 = h2 + RH * AW;     // AH x AW: box(x) then a
+  float* m2 = m1 + AH * AW;     //          box(g) then b
+
+  const long long bi = plane / q.Co;
+  const int c = (int)(plane % q.Co);
+  const float* xs = x + (bi * q.Cx + (q.Cx == 1 ? 0 : c)) * HW;
+  const float* gs = guide + (bi * q.Cg + (q.Cg == 1 ? 0 : c)) * HW;
+  for (int i = threadIdx.x; i < RH * RW; i += blockDim.x) {
+    const int ly = i / RW, lx = i - ly * RW;
+    const int gy = ty0 - 2 * q.R + ly, gx = tx0 - 2 * q.R + lx;
+    float vx = 0.f, vg = 0.f;
+    if ((unsigned)gy < (unsigned)q.H && (unsigned)gx < (unsigned)q.W) {
+      const long long px = (long long)gy * q.W + gx;
+      vx = xs[px];
+      vg = gs[px];
+    }
+    X[i] = vx;
+    G[i] = vg;
+  }
+  __syncthreads();
+
+  row_sums<false>(X, G, h1, h2, RH, RW, AW, q.R, r);
+  for (int i = threadIdx.x; i < AH * AW; i += blockDim.x) {
+    const int ra = i / AW, ca = i - ra * AW;
+    m1[i] = col_sum(h1, RH, AW, ra + q.R, ca, r) / kk;
+    m2[i] = col_sum(h2, RH, AW, ra + q.R, ca, r) / kk;
+  }
+  __syncthreads();
+  row_sums<true>(X, G, h1, h2, RH, RW, AW, q.R, r);
+  for (int i = threadIdx.x; i < AH * AW; i += blockDim.x) {
+    const int ra = i / AW, ca = i - ra * AW;
+    const int gy = ty0 - q.R + ra, gx = tx0 - q.R + ca;
+    float a = 0.f, b = 0.f;
+    if ((unsigned)gy < (unsigned)q.H && (unsigned)gx < (unsigned)q.W) {
+      const float mean_x = m1[i], mean_g = m2[i];
+      const float corr_xg = col_sum(h1, RH, AW, ra + q.R, ca, r) / kk;
+      const float corr_gg = col_sum(h2, RH, AW, ra + q.R, ca, r) / kk;
+      a = (corr_xg - mean_x * mean_g) / (corr_gg - mean_g * mean_g + eps);
+      b = mean_x - a * mean_g;
+    }
+    m1[i] = a;
+    m2[i] = b;
+  }
+  __syncthreads();
+  row_sums<false>(m1, m2, h1, h2, AH, AW, q.TW, q.R, r);
+  float* dst = out + plane * HW;
+  for (int i = threadIdx.x; i < q.TH * q.TW; i += blockDim.x) {
+    const int ty = i / q.TW, tx = i - ty * q.TW;
+    const int gy = ty0 + ty, gx = tx0 + tx;
+    if (gy < q.H && gx < q.W) {
+      const float mean_a = col_sum(h1, AH, q.TW, ty + q.R, tx, r) / kk;
+      const float mean_b = col_sum(h2, AH, q.TW, ty + q.R, tx, r) / kk;
+      dst[(long long)gy * q.W + gx] = mean_a * G[(ty + 2 * q.R) * RW + tx + 2 * q.R] + mean_b;
+    }
+  }
+}
+
+// f32 words of LDS of one workgroup.
+static long long guided_lds_words(int TH, int TW, int R) {
+  const long long RH = TH + 4 * R, RW = TW + 4 * R, AH = TH + 2 * R, AW = TW + 2 * R;
+  return 2 * RH * RW + 2 * RH * AW + 2 * AH * AW;
+}
+
+// Rows of a tile of the tiled form: 64 up to radius 6, then the largest of 32, 16, 8 whose working set fits the
+// LDS (32 up to radius 11, 16 up to 14, 8 for 15 and 16).  The tile stays 64 columns wide.
+static int guided_tile_rows(int radius) {
+  for (int th = kPostTile; th >= 8; th /= 2)
+    if (guided_lds_words(th, kPostTile, radius) * 4 <= kPostLds) return th;
+  return 0;
+}
+
+}  // namespace hiseg
+
+extern "C" int hiseg_guided_filter_fwd(const float* x, const float* guide, float* out, long long B, int Cx, int Cg,
+                                       int H, int W, int radius, float eps, int force_tiled, hiseg_stream_t stream) {
+  HISEG_REQUIRE(radius >= 1 && radius <= kGuidedMaxRadius, HISEG_ERR_BAD_ARG, "guided_filter: radius %d (1..%d)",
+                radius, kGuidedMaxRadius);
+  if (!guide) Cg = Cx;
+  HISEG_REQUIRE(Cx >= 0 && Cg >= 0 && (Cx == Cg || Cx == 1 || Cg == 1), HISEG_ERR_BAD_ARG,
+                "guided_filter: channels %d and %d do not broadcast", Cx, Cg);
+  HISEG_REQUIRE(B >= 0 && H >= 0 && W >= 0 && (long long)H * W <= 0x7fffffffll, HISEG_ERR_BAD_SHAPE,
+                "guided_filter: batch %lld H %d W %d", B, H, W);
+  const int Co = Cx > Cg ? Cx : Cg;
+  if (B == 0 || Cx == 0 || Cg == 0 || H == 0 || W == 0) return HISEG_OK;
+  HISEG_REQUIRE(x && out, HISEG_ERR_BAD_ARG, "guided_filter: null pointer");
+  HISEG_REQUIRE(out != x && out != guide, HISEG_ERR_BAD_ARG, "guided_filter: out aliases an input");
+  GuidedGeom q;
+  q.H = H; q.W = W; q.Cx = Cx; q.Cg = Cg; q.Co = Co;
+  unsigned block;
+  if (!force_tiled && (long long)H * W <= kGuidedResidentPx) {
+    q.TH = H; q.TW = W; q.tiles_x = 1; q.tiles = 1; q.R = 0;
+    block = H * W >= 1024 ? 1024u : (unsigned)((H * W + 63) / 64 * 64);
+  } else {
+    q.TH = guided_tile_rows(radius);
+    HISEG_REQUIRE(q.TH > 0, HISEG_ERR_BAD_ARG, "guided_filter: radius %d does not fit the LDS", radius);
+    q.TW = kPostTile;
+    q.R = radius;
+    q.tiles_x = (W + q.TW - 1) / q.TW;
+    q.tiles = q.tiles_x * ((H + q.TH - 1) / q.TH);
+    block = 1024;
+  }
+  HISEG_REQUIRE(B <= 0x7fffffffll / Co && B * Co <= 0x7fffffffll / q.tiles, HISEG_ERR_BAD_SHAPE,
+                "guided_filter: %lld planes of %d tiles", B * Co, q.tiles);
+  const size_t lds = (size_t)guided_lds_words(q.TH, q.TW, q.R) * sizeof(float);
+  (void)hipFuncSetAttribute((const void*)guided_filter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kPostLds);
+  hipLaunchKernelGGL(guided_filter_kernel, dim3((unsigned)(B * Co * q.tiles)), dim3(block), lds, (hipStream_t)stream,
+                     x, guide ? guide : x, out, q, radius, eps);
+  return hiseg_check_launch("guided_filter");
+}

@@ -26,7 +26,7 @@ from .metrics import (  # noqa: F401,E402
 from .distill import (  # noqa: F401,E402
     DistillationUNetWrapper, UNetDecoderOnly, UNetDistillationLoss, create_unet_distillation_model)
 from .postprocess import (  # noqa: F401,E402
-    BilateralFilter, BinaryMaskBilateralFilter, BinaryMaskEdgeSmoothing, FastBilateralFilter,
+    BilateralFilter, BinaryMaskBilateralFilter, BinaryMaskEdgeSmoothing, EdgePreservingFilter, FastBilateralFilter,
     MorphologicalBilateralFilter, MultiClassEdgeSmoothing, apply_edge_smoothing_to_masks)
 
 __version__ = "0.2.0"

@@ -380,6 +380,7 @@ def _declare(lib):
                                       c_int, P], c_int),
         "hiseg_morph_bilateral_fwd": ([P, P, c_ll, c_int, c_int, c_int, c_float, c_int, c_int, P], c_int),
         "hiseg_bilateral_fwd": ([P, P, c_ll, c_int, c_int, c_int, c_float, c_float, P], c_int),
+        "hiseg_guided_filter_fwd": ([P, P, P, c_ll, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P], c_int),
         # ---- boundary refinement stage and active-contour loss (include/hiseg_refine.h)
         "hiseg_edge_map_ws": ([c_int, c_int, c_int], c_ll),
         "hiseg_edge_map_fwd": ([P, c_int, c_int, c_int, P, P, P, P, c_int, c_int, P, P], c_int),

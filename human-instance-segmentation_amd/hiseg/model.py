@@ -210,14 +210,20 @@ class RGBHierarchicalExportWrapper(nn.Module):
     ROIAlign scales are set to (H, W) as _adjust_roi_align_spatial_scale does (:80-98).  The reference runs the
     full-image UNet twice (once for binary_masks, once inside the model); both passes are the same deterministic
     function of the image, so it is computed once here.
+
+    ``binary_post`` / ``instance_post``: optional callables of one tensor (any module of hiseg.postprocess; a
+    guided filter here is self-guided), applied to binary_masks / instance_masks before they are returned.  They are
+    not part of a traced export.
     """
 
     def __init__(self, model: HierarchicalRGBSegmentationModelWithFullImagePretrainedUNet, image_size=None,
-                 dilation_pixels: int = 0):
+                 dilation_pixels: int = 0, binary_post=None, instance_post=None):
         super().__init__()
         self.model = model
         self.image_size = image_size
         self.dilation_pixels = dilation_pixels
+        self.binary_post = binary_post
+        self.instance_post = instance_post
 
     def forward(self, images: torch.Tensor, rois: torch.Tensor):
         H, W = images.shape[-2:] if self.image_size is None else self.image_size
@@ -225,8 +231,17 @@ class RGBHierarchicalExportWrapper(nn.Module):
             m.spatial_scale = (H, W)
             m.spatial_scale_h, m.spatial_scale_w = H, W
         if export.tracing(images, rois):
+            for hook in ("binary_post", "instance_post"):
+                if getattr(self, hook) is not None:
+                    raise NotImplementedError(f"{hook} is set: the mask post-processing ops have no traced form; "
+                                              "export the wrapper without it")
             return export.traced_export(self, images, rois)
-        return engine.export_forward(self.model, images, rois, self.dilation_pixels)
+        inst, binary = engine.export_forward(self.model, images, rois, self.dilation_pixels)
+        if self.instance_post is not None:
+            inst = self.instance_post(inst)
+        if self.binary_post is not None:
+            binary = self.binary_post(binary)
+        return inst, binary
 
 
 class StreamPipelinedExport:
@@ -234,7 +249,9 @@ class StreamPipelinedExport:
     latency-bound depthwise, SE and narrow decoder kernels) runs on one stream while the ROI head of batch k
     (MFMA-bound 256-channel convs) runs on the other, so the two kernel classes share the CUs instead of
     alternating.  Every batch still runs the complete contract; results are identical to
-    ``RGBHierarchicalExportWrapper(model)(images, rois)`` per batch (same kernels, same inputs).
+    ``RGBHierarchicalExportWrapper(model)(images, rois)`` per batch (same kernels, same inputs).  The wrapper's
+    ``binary_post`` / ``instance_post`` run on the stream that produced their tensor (UNet / head), so the filter
+    of batch k overlaps the other stream's work.
 
     ``run(batches)`` takes an iterable of (images, rois) and returns [(instance_masks, binary_masks), ...],
     ready on the caller's current stream when it returns (the caller synchronises as usual).
@@ -289,10 +306,14 @@ class StreamPipelinedExport:
                 u, binary = engine.export_unet_phase(w.model, images)
                 ready = torch.cuda.Event()
                 ready.record(self.s_unet)
+                if w.binary_post is not None:    # behind `ready`: the head does not wait for it
+                    binary = w.binary_post(binary)
             with torch.cuda.stream(self.s_head):
                 self.s_head.wait_event(ready)
                 u.record_stream(self.s_head)
                 inst = engine.export_head_phase(w.model, images, rois, u, w.dilation_pixels)
+                if w.instance_post is not None:
+                    inst = w.instance_post(inst)
             outs.append((inst, binary))
         caller.wait_stream(self.s_unet)
         caller.wait_stream(self.s_head)
@@ -329,6 +350,9 @@ class StreamPipelinedExport:
         for k, (images, rois) in enumerate(batches):
             ready = torch.cuda.Event()
             ready.record(self.s_unet)
+            if w.binary_post is not None:    # behind `ready`, ahead of the next batch's UNet chunks
+                with torch.cuda.stream(self.s_unet):
+                    binary = w.binary_post(binary)
             nxt = None
             if k + 1 < len(batches):
                 self._set_scale(batches[k + 1][0])
@@ -343,6 +367,8 @@ class StreamPipelinedExport:
                     inst = engine.export_head_phase(w.model, images, rois, u, w.dilation_pixels)
                 finally:
                     ops.GATE = None
+                if w.instance_post is not None:
+                    inst = w.instance_post(inst)
             outs.append((inst, binary))
             if nxt is not None:
                 u, binary = g.finish()

@@ -743,6 +743,29 @@ def bilateral(x: torch.Tensor, kernel_size: int = 5, sigma_spatial: float = 1.0,
     return out
 
 
+def guided_filter(x: torch.Tensor, guide: Optional[torch.Tensor] = None, radius: int = 2, eps: float = 0.01,
+                  force_tiled: bool = False) -> torch.Tensor:
+    """EdgePreservingFilter: [B,Cx,H,W] x guided by [B,Cg,H,W] (None: by itself) -> f32 [B,max(Cx,Cg),H,W]; the
+    channels broadcast as in x * guide."""
+    _require_gpu(x, guide)
+    for t, what in ((x, "x"), (guide, "guide")):
+        if t is not None and t.dim() != 4:
+            raise ValueError(f"guided_filter: expected a (B, C, H, W) {what}, got shape {tuple(t.shape)}")
+    B, Cx, H, W = x.shape
+    Cg = Cx
+    if guide is not None:
+        Cg = guide.shape[1]
+        if (guide.shape[0], *guide.shape[2:]) != (B, H, W) or not (Cx == Cg or Cx == 1 or Cg == 1):
+            raise ValueError(f"guided_filter: x {tuple(x.shape)} and guide {tuple(guide.shape)} do not broadcast "
+                             "over the channels")
+        guide = guide.to(torch.float32).contiguous()
+    x = x.to(torch.float32).contiguous()
+    out = torch.empty(B, max(Cx, Cg), H, W, dtype=torch.float32, device=x.device)
+    L.check(L.lib().hiseg_guided_filter_fwd(x.data_ptr(), _ptr(guide), out.data_ptr(), B, Cx, Cg, H, W, radius, eps,
+                                            int(force_tiled), L.stream_ptr()), "guided_filter")
+    return out
+
+
 # ---- boundary refinement stage (include/hiseg_refine.h): f32 NCHW logits [N,3,H,W]
 
 

@@ -11,14 +11,14 @@ path: a CPU tensor raises ``RuntimeError``.
 Differences from the reference, all on inputs it mishandles or leaves to chance:
   * ``MorphologicalBilateralFilter`` works on any channel count (the reference's conv weight fixes C = 1) and
     refuses even ``kernel_size`` / ``morph_size`` (the reference returns a plane of another size);
-  * ``kernel_size`` is limited to 3..9 (``morph_size`` 1..9);
+  * ``kernel_size`` is limited to 3..9 (``morph_size`` 1..9), the ``radius`` of ``EdgePreservingFilter`` to 1..16;
   * ``MultiClassEdgeSmoothing.smooth_predictions(apply_softmax=True)``: with 3 classes the softmax is skipped, as
     the argmax of the scores is the argmax of their softmax; with another class count it is not implemented;
   * NaN scores in the 3-class path are out of scope (hiseg_post.h).
 """
 from __future__ import annotations
 
-from typing import Union
+from typing import Optional, Union
 
 import numpy as np
 import torch
@@ -27,7 +27,7 @@ import torch.nn as nn
 from . import ops
 
 __all__ = ["BinaryMaskEdgeSmoothing", "MultiClassEdgeSmoothing", "apply_edge_smoothing_to_masks", "BilateralFilter",
-           "FastBilateralFilter", "BinaryMaskBilateralFilter", "MorphologicalBilateralFilter"]
+           "FastBilateralFilter", "EdgePreservingFilter", "BinaryMaskBilateralFilter", "MorphologicalBilateralFilter"]
 
 
 def _check_kernel_size(kernel_size: int, what: str = "Kernel size", lo: int = 3) -> None:
@@ -164,6 +164,30 @@ class FastBilateralFilter(nn.Module):
             return x
         return ops.var_gated_blur(x, self.kernel_size, self.sigma_spatial, 1.0 / (2 * self.sigma_range ** 2),
                                   self.num_iterations)
+
+
+class EdgePreservingFilter(nn.Module):
+    """Guided filter (bilateral_filter.py:219-296): x smoothed where ``guide`` (default: x itself) is flat, kept
+    where it has edges.  (B, C, H, W) or (C, H, W) in; the channels of x and guide broadcast as in ``x * guide``."""
+
+    def __init__(self, radius: int = 2, eps: float = 0.01):
+        super().__init__()
+        if not 1 <= radius <= 16:
+            raise ValueError(f"radius must be in 1..16, got {radius}")
+        self.radius = radius
+        self.eps = eps
+        self.kernel_size = 2 * radius + 1
+        kernel = torch.ones(1, 1, self.kernel_size, self.kernel_size)
+        self.register_buffer("box_kernel", kernel / (self.kernel_size ** 2))
+
+    def forward(self, x: torch.Tensor, guide: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if x.dim() not in (3, 4) or (guide is not None and guide.dim() != x.dim()):
+            raise ValueError("EdgePreservingFilter: expected (B, C, H, W) or (C, H, W) tensors of one rank, got "
+                             f"{tuple(x.shape)}" + ("" if guide is None else f" and {tuple(guide.shape)}"))
+        if x.dim() == 3:
+            return ops.guided_filter(x.unsqueeze(0), None if guide is None else guide.unsqueeze(0), self.radius,
+                                     self.eps).squeeze(0)
+        return ops.guided_filter(x, guide, self.radius, self.eps)
 
 
 class BinaryMaskBilateralFilter(nn.Module):

@@ -67,6 +67,25 @@ int hiseg_morph_bilateral_fwd(const float* x, float* out, long long NC, int H, i
 int hiseg_bilateral_fwd(const float* x, float* out, long long NC, int H, int W, int kernel_size,
                         float sigma_spatial, float sigma_range, hiseg_stream_t stream);
 
+/* EdgePreservingFilter.forward (bilateral_filter.py:263-296), the guided filter: x [B][Cx][H][W], guide
+ * [B][Cg][H][W] -> out [B][max(Cx, Cg)][H][W].  With box(t) the (2 radius + 1)^2 sum of t, zero padded and always
+ * divided by (2 radius + 1)^2:
+ *   a = (box(x*g) - box(x)*box(g)) / (box(g*g) - box(g)^2 + eps),  b = box(x) - a*box(g),  out = box(a)*g + box(b).
+ * The variance is not clamped, and a and b are zero outside the image for the second pair of boxes, as the
+ * reference's zero-padded convolutions have it.  guide == NULL: self-guided (g = x, Cg is ignored); guide may equal
+ * x, out is distinct from both.  Channels broadcast as in x * guide: Cx == Cg or one of them is 1, else
+ * HISEG_ERR_BAD_ARG; a plane that is broadcast is read once per output plane and never materialised.  radius 1..16.
+ * Every box is a separable plain f32 sum (rows, then columns, taps in ascending order), independent of the tile.
+ *
+ * Forms.  The working set is six f32 planes (x, g, two planes of row sums, and box(x), box(g) that become a, b), so
+ * a plane of at most 6826 pixels (160 KB / 24 B: the 64x48 instance masks; the 128x96 ones are tiled) is owned by
+ * one workgroup and read from memory once.  Larger planes, or any with force_tiled != 0, take tiles 64 pixels wide
+ * that recompute a and b on a halo of radius from inputs on a halo of 2 radius; the tile is 64 rows high up to
+ * radius 6 and 32 / 16 / 8 rows up to radius 11 / 14 / 16, where 64 rows would not fit the LDS.  Both forms give the
+ * same bits. */
+int hiseg_guided_filter_fwd(const float* x, const float* guide, float* out, long long B, int Cx, int Cg, int H, int W,
+                            int radius, float eps, int force_tiled, hiseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

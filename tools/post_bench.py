@@ -14,6 +14,10 @@ would run them on the GPU.  BilateralFilter has no torch composition short of an
 is what is timed.  Outputs are compared once per filter and shape (fraction of differing pixels for thresholded
 outputs, max |diff| for soft ones) so that the two columns time the same function.
 
+The guided filter (EdgePreservingFilter) is timed the same way at the 64x48, 128x96 and 480x640 planes, self-guided
+and under a 3-channel guide (guided_rows; --guided runs only these).  --pipeline times the pipelined C2 serving step
+of bench.py as it is, with binary_post riding on the UNet stream, and followed by the same filter (pipeline_rows).
+
 Prints one JSON object; --markdown adds the table for DESIGN.md.
 """
 import argparse
@@ -114,14 +118,107 @@ def time_us(fn):
     return statistics.median(windows), min(windows), max(windows)
 
 
+def t_guided(x, guide, radius=2, eps=0.01):
+    k = 2 * radius + 1
+    box_k = torch.full((1, 1, k, k), 1.0 / (k * k), device=x.device)
+
+    def box(t):
+        return F.conv2d(t.reshape(-1, 1, *t.shape[-2:]), box_k, padding=radius).reshape(t.shape)
+    g = x if guide is None else guide
+    mean_x, mean_g = box(x), box(g)
+    a = (box(x * g) - mean_x * mean_g) / (box(g * g) - mean_g * mean_g + eps)
+    b = mean_x - a * mean_g
+    return box(a) * g + box(b)
+
+
+GUIDED_SHAPES = {"roi 256x1x64x48": (256, 1, 64, 48), "mask 256x1x128x96": (256, 1, 128, 96),
+                 "full 32x1x480x640": (32, 1, 480, 640)}
+
+
+def guided_rows(dev, gen):
+    """EdgePreservingFilter (defaults: radius 2, eps 0.01) on the C2 planes, self-guided (8 bytes per pixel: one
+    plane read, one written) and guided by a 3-channel image (28: the mask, three guide planes read, three output
+    planes written).  64x48 is the resident form; 128x96 and 480x640 are tiled."""
+    rows = []
+    mod = hiseg.EdgePreservingFilter().to(dev)
+    for sname, shape in GUIDED_SHAPES.items():
+        B, _, H, W = shape
+        yy, xx = torch.meshgrid(torch.linspace(-1, 1, H, device=dev), torch.linspace(-1, 1, W, device=dev), indexing="ij")
+        soft = torch.sigmoid(4 * (1 - ((yy / 0.6) ** 2 + (xx / 0.5) ** 2))).expand(shape).contiguous()
+        rgb = torch.rand(B, 3, H, W, device=dev, generator=gen)
+        for name, guide, bpp in (("guided_filter r2 (self-guided)", None, 8), ("guided_filter r2 (RGB guide)", rgb, 28)):
+            with torch.no_grad():
+                diff = float((mod(soft, guide) - t_guided(soft, guide)).abs().max())
+                us, lo, hi = time_us(lambda: mod(soft, guide))
+                tus, tlo, thi = time_us(lambda: t_guided(soft, guide))
+            rows.append({"filter": name, "shape": sname, "hiseg_us": round(us, 1), "hiseg_us_min_max": [round(lo, 1), round(hi, 1)],
+                         "torch_us": round(tus, 1), "torch_us_min_max": [round(tlo, 1), round(thi, 1)],
+                         "speedup": round(tus / us, 2), "bytes_per_pixel": bpp,
+                         "hbm_peak_fraction": round(B * H * W * bpp / (us * 1e-6) / HBM_PEAK, 4), "max_abs_diff": diff})
+    return rows
+
+
+def pipeline_rows(dev, steps=20, warmup=5, repeats=5):
+    """The pipelined C2 serving step (bench.py's model and batch, bf16) three ways: as it is, with
+    binary_post = EdgePreservingFilter() riding on the UNet stream, and as it is followed by the same filter on
+    the caller's stream.  ms per step: host clock around `steps` steps ending in a synchronise, median of
+    `repeats` windows."""
+    import time
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden"))
+    import bench
+    model = bench.build_model(dev, torch.bfloat16)
+    images, rois = bench.synthetic_batch(dev, 0)
+    post = hiseg.EdgePreservingFilter().to(dev)
+    plain = hiseg.StreamPipelinedExport(hiseg.RGBHierarchicalExportWrapper(model))
+    hooked = hiseg.StreamPipelinedExport(hiseg.RGBHierarchicalExportWrapper(model, binary_post=post))
+
+    def run_plain(k):
+        return plain.run([(images, rois)] * k)
+
+    def run_hooked(k):
+        return hooked.run([(images, rois)] * k)
+
+    def run_after(k):
+        return [(inst, post(binary)) for inst, binary in plain.run([(images, rois)] * k)]
+    variants = (("pipelined step", run_plain), ("pipelined step, binary_post hook", run_hooked),
+                ("pipelined step, then the filter", run_after))
+    times = {name: [] for name, _ in variants}
+    with torch.no_grad():
+        a, b = run_hooked(2)[-1], run_after(2)[-1]
+        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+        for _, fn in variants:
+            fn(warmup)
+        torch.cuda.synchronize()
+        for _ in range(repeats):          # alternate the variants: the machine is shared
+            for name, fn in variants:
+                t0 = time.perf_counter()
+                fn(steps)
+                torch.cuda.synchronize()
+                times[name].append((time.perf_counter() - t0) / steps * 1e3)
+    return [{"schedule": name, "ms_per_step": round(statistics.median(t), 3),
+             "ms_per_step_min_max": [round(min(t), 3), round(max(t), 3)]} for name, t in times.items()]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--markdown", action="store_true")
+    ap.add_argument("--guided", action="store_true", help="only the guided filter rows")
+    ap.add_argument("--pipeline", action="store_true", help="only the pipelined serving step with / without binary_post")
     args = ap.parse_args()
     dev = torch.device("cuda")
     gen = torch.Generator(device=dev).manual_seed(11)
+    if args.pipeline:
+        rows = pipeline_rows(dev)
+        print(json.dumps({"steps": 20, "warmup": 5, "repeats": 5, "rows": rows}))
+        if args.markdown:
+            print("| schedule | ms per step (min - max) |")
+            print("|---|---|")
+            for r in rows:
+                print(f"| {r['schedule']} | {r['ms_per_step']} ({r['ms_per_step_min_max'][0]} - {r['ms_per_step_min_max'][1]}) |")
+        return
     rows = []
-    for sname, shape in SHAPES.items():
+    for sname, shape in ({} if args.guided else SHAPES).items():
         B, _, H, W = shape
         yy, xx = torch.meshgrid(torch.linspace(-1, 1, H, device=dev), torch.linspace(-1, 1, W, device=dev), indexing="ij")
         field = 1 - ((yy / 0.6) ** 2 + (xx / 0.5) ** 2)
@@ -155,6 +252,7 @@ def main():
                          "speedup": round(tus / us, 2), "bytes_per_pixel": bpp,
                          "hbm_peak_fraction": round(px * bpp / (us * 1e-6) / HBM_PEAK, 4),
                          ("max_abs_diff" if soft_out else "pixels_differing"): diff})
+    rows += guided_rows(dev, gen)
     print(json.dumps({"hbm_peak_Bps": HBM_PEAK, "warmup": WARMUP, "repeats": REPEATS, "calls": CALLS, "rows": rows}))
     if args.markdown:
         print("| filter | shape | hiseg us | torch composition us | x | HBM peak fraction |")
