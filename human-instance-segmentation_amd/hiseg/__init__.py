@@ -16,6 +16,8 @@ from .model import (  # noqa: F401
     create_rgb_hierarchical_model)
 
 from .losses import RefinedHierarchicalLoss, active_contour_term  # noqa: F401,E402
+from .distance_loss import (  # noqa: F401,E402
+    AdaptiveBoundaryLoss, DistanceAwareSegmentationLoss, create_distance_aware_loss)
 from .optim import FusedAdamW, cosine_lr  # noqa: F401,E402
 from .graphs import GraphedStep, GraphedBranchStep  # noqa: F401,E402
 from .checkpoint import resume_from_checkpoint, save_checkpoint  # noqa: F401,E402

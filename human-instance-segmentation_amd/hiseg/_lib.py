@@ -392,6 +392,15 @@ def _declare(lib):
         "hiseg_active_contour_ws": ([c_int, c_int, c_int], c_ll),
         "hiseg_active_contour_fwd": ([P, c_int, c_int, c_int, P, P, P], c_int),
         "hiseg_active_contour_bwd": ([P, c_int, c_int, c_int, P, P, P, P], c_int),
+        # ---- distance transform, boundary weight map and distance-aware loss (include/hiseg_distance.h)
+        "hiseg_distance_resident": ([c_int, c_int], c_int),
+        "hiseg_distance_ws": ([c_int, c_int, c_int], c_ll),
+        "hiseg_distance_transform": ([P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P], c_int),
+        "hiseg_distance_weight_map": ([P, c_int, c_int, c_int, c_int, P, ctypes.c_double, ctypes.c_double, P, P, P,
+                                       c_int, P, P, P, P], c_int),
+        "hiseg_distance_loss_fwd": ([P, P, P, c_int, c_int, c_int, P, c_int, c_float, c_float, c_float, P, P, P],
+                                    c_int),
+        "hiseg_distance_loss_bwd": ([P, P, P, c_int, c_int, c_int, P, c_int, c_float, P, P, P, P], c_int),
         "hiseg_optim_blocks": ([], c_int),
         "hiseg_grad_norm_partials": ([P, c_ll, P, P], c_int),
         "hiseg_adamw_step": ([P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_float, c_float, c_float, P,

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .distance_loss import AdaptiveBoundaryLoss, DistanceAwareSegmentationLoss
 from .losses import LazyLossDict
 
 
@@ -173,7 +174,8 @@ def evaluate_model(model, dataloader, loss_fn, device: str, feature_extractor: O
                    config: Optional[object] = None, epoch: Optional[int] = None,
                    output_dir: Optional[object] = None) -> Dict[str, object]:
     """train_utils.py:109-402 for the RGB hierarchical model: ``model(images, rois) -> (logits, aux)``,
-    ``loss_fn(logits, masks, aux) -> (loss, loss_dict)``; batches are dicts with 'image', 'roi_boxes',
+    ``loss_fn(logits, masks, aux) -> (loss, loss_dict)`` (the distance-aware losses take the batch's
+    'instance_info' as the third argument instead); batches are dicts with 'image', 'roi_boxes',
     'roi_masks'.  Returns the reference's keys.  No host synchronisation inside the loop."""
     if config is not None:
         mc = getattr(config, "model", None)
@@ -194,10 +196,12 @@ def evaluate_model(model, dataloader, loss_fn, device: str, feature_extractor: O
             predictions = model(images, rois)
             if isinstance(predictions, tuple):
                 logits, aux = predictions
-                loss, loss_dict = loss_fn(logits, masks, aux)
             else:
-                logits = predictions
-                loss, loss_dict = loss_fn(logits, masks, {})
+                logits, aux = predictions, {}
+            if isinstance(loss_fn, (DistanceAwareSegmentationLoss, AdaptiveBoundaryLoss)):   # train_utils.py:194-226
+                loss, loss_dict = loss_fn(logits, masks, batch.get("instance_info"))
+            else:
+                loss, loss_dict = loss_fn(logits, masks, aux)
             losses.append(loss.detach().reshape(()))
             dicts.append(loss_dict)
             acc.update(logits, masks)

@@ -838,3 +838,91 @@ def boundary_refine_fused(em: EdgeMap, blend, w1, s1, t1, w2_frag, s2, t2, w3, b
         out.data_ptr(), L.stream_ptr()), "boundary_refine_fused")
     FUSED_REFINE_CALLS[0] += 1
     return out
+
+
+# ------------------------------------------------------------------ distance transform (include/hiseg_distance.h)
+_DIST_TABLES = {}
+
+
+def _distance_table(width: int, device) -> torch.Tensor:
+    """(1 - sqrt(d2) / width) for d2 in [0, width^2), evaluated on the host in double as the reference evaluates it
+    (distance_aware_loss.py:172-174); uploaded once per (width, device)."""
+    key = (int(width), str(device))
+    t = _DIST_TABLES.get(key)
+    if t is None:
+        d = torch.sqrt(torch.arange(width * width, dtype=torch.float64))
+        t = _DIST_TABLES[key] = (1.0 - d / width).to(device)
+    return t
+
+
+def _distance_targets(mask: torch.Tensor, what: str):
+    _require_gpu(mask)
+    if mask.dim() == 2:
+        mask = mask[None]
+    if mask.dim() != 3:
+        raise ValueError(f"{what}: expected a class mask [H,W] or [N,H,W], got shape {tuple(mask.shape)}")
+    return mask.to(torch.int64).contiguous()
+
+
+def boundary_distance(mask: torch.Tensor, max_distance: float = 10.0, *, force_tiled: bool = False,
+                      return_d2: bool = False):
+    """DistanceTransform.compute_boundary_distance (distance_aware_loss.py:13-50) for class masks [H,W] or [N,H,W]
+    with values 0, 1, 2: the exact Euclidean distance to the nearest boundary site clipped to ``max_distance``, as a
+    float64 tensor of the mask's shape (``return_d2``: also the int32 squared distance, capped).  The site rule --
+    per sample -- and the result for a mask without sites are those of the reference (include/hiseg_distance.h).
+    ``max_distance >= max(H, W)`` gives the unclipped transform."""
+    squeeze = mask.dim() == 2
+    t = _distance_targets(mask, "boundary_distance")
+    N, H, W = t.shape
+    if not max_distance > 0:
+        raise ValueError(f"boundary_distance: max_distance {max_distance}")
+    import math
+    radius = min(int(math.ceil(max_distance)), max(H, W))
+    d2cap = min((radius + 1) ** 2, 2 ** 30) if radius < max(H, W) else 2 ** 30
+    lib = L.lib()
+    d2 = torch.empty(N, H, W, dtype=torch.int32, device=t.device)
+    ws = torch.empty(int(lib.hiseg_distance_ws(N, H, W)), dtype=torch.float32, device=t.device)
+    L.check(lib.hiseg_distance_transform(t.data_ptr(), N, H, W, radius, d2cap, int(force_tiled), d2.data_ptr(),
+                                         ws.data_ptr(), L.stream_ptr()), "distance_transform")
+    dist = torch.sqrt(d2.to(torch.float64)).clamp_(max=float(max_distance))
+    if squeeze:
+        dist, d2 = dist[0], d2[0]
+    return (dist, d2) if return_d2 else dist
+
+
+def boundary_weight_map(mask: torch.Tensor, boundary_width: int = 5, boundary_weight: float = 2.0,
+                        instance_sep_weight: float = 3.0, instance_distances: Optional[torch.Tensor] = None,
+                        instance_present: Optional[torch.Tensor] = None, *,
+                        dev_weights: Optional[torch.Tensor] = None, force_tiled: bool = False):
+    """BoundaryWeightGenerator.generate_weights (distance_aware_loss.py:147-185) for class masks [N,H,W] (or [H,W]).
+    Returns (weights f32, d2 int32) of the mask's shape: d2 is the squared distance to the nearest boundary site
+    capped at boundary_width^2.  ``instance_distances`` f32 [N,H,W] with ``instance_present`` uint8 [N] (all present
+    when None) multiplies the weight by instance_sep_weight where the map is < 50.  ``dev_weights``: device float
+    [2] read in place of the two weight arguments (AdaptiveBoundaryLoss)."""
+    squeeze = mask.dim() == 2
+    t = _distance_targets(mask, "boundary_weight_map")
+    N, H, W = t.shape
+    width = int(boundary_width)
+    if width < 1:
+        raise ValueError(f"boundary_weight_map: boundary_width {boundary_width}")
+    lib, dev = L.lib(), t.device
+    inst = pres = None
+    if instance_distances is not None:
+        _require_gpu(instance_distances, instance_present)
+        inst = instance_distances.to(torch.float32).reshape(N, H, W).contiguous()
+        pres = (torch.ones(N, dtype=torch.uint8, device=dev) if instance_present is None
+                else instance_present.to(torch.uint8).reshape(N).contiguous())
+    if dev_weights is not None:
+        _require_gpu(dev_weights)
+        assert dev_weights.dtype == torch.float32 and dev_weights.numel() == 2 and dev_weights.is_contiguous()
+    d2 = torch.empty(N, H, W, dtype=torch.int32, device=dev)
+    w = torch.empty(N, H, W, dtype=torch.float32, device=dev)
+    ws = torch.empty(int(lib.hiseg_distance_ws(N, H, W)), dtype=torch.float32, device=dev)
+    table = _distance_table(width, dev)
+    L.check(lib.hiseg_distance_weight_map(t.data_ptr(), N, H, W, width, table.data_ptr(), float(boundary_weight),
+                                          float(instance_sep_weight), _ptr(dev_weights), _ptr(inst), _ptr(pres),
+                                          int(force_tiled), d2.data_ptr(), w.data_ptr(), ws.data_ptr(),
+                                          L.stream_ptr()), "distance_weight_map")
+    if squeeze:
+        w, d2 = w[0], d2[0]
+    return w, d2
