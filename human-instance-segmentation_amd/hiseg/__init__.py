@@ -30,6 +30,7 @@ from .distill import (  # noqa: F401,E402
 from .postprocess import (  # noqa: F401,E402
     BilateralFilter, BinaryMaskBilateralFilter, BinaryMaskEdgeSmoothing, EdgePreservingFilter, FastBilateralFilter,
     MorphologicalBilateralFilter, MultiClassEdgeSmoothing, apply_edge_smoothing_to_masks)
+from .compose import InstanceMapComposer, instance_colors  # noqa: F401,E402
 
 __version__ = "0.2.0"
 

@@ -401,6 +401,12 @@ def _declare(lib):
         "hiseg_distance_loss_fwd": ([P, P, P, c_int, c_int, c_int, P, c_int, c_float, c_float, c_float, P, P, P],
                                     c_int),
         "hiseg_distance_loss_bwd": ([P, P, P, c_int, c_int, c_int, P, c_int, c_float, P, P, P, P], c_int),
+        # ---- full-frame instance composition (include/hiseg_compose.h)
+        "hiseg_compose_words_per_row": ([c_int], c_int),
+        "hiseg_roi_mask_classify_fwd": ([P, c_ll, c_int, c_int, c_float, P, P, P, P], c_int),
+        "hiseg_roi_mask_pack_fwd": ([P, c_ll, c_int, c_int, P, P, P, P], c_int),
+        "hiseg_instance_map_fwd": ([P, P, P, c_ll, c_int, c_int, c_int, c_int, c_int, P, P], c_int),
+        "hiseg_instance_overlay_fwd": ([P, P, P, c_ll, c_int, c_int, c_int, ctypes.c_double, P, P], c_int),
         "hiseg_optim_blocks": ([], c_int),
         "hiseg_grad_norm_partials": ([P, c_ll, P, P], c_int),
         "hiseg_adamw_step": ([P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_float, c_float, c_float, P,

@@ -214,16 +214,30 @@ class RGBHierarchicalExportWrapper(nn.Module):
     ``binary_post`` / ``instance_post``: optional callables of one tensor (any module of hiseg.postprocess; a
     guided filter here is self-guided), applied to binary_masks / instance_masks before they are returned.  They are
     not part of a traced export.
+
+    ``compose``: optional hiseg.InstanceMapComposer.  With one, forward returns a third tensor ``instance_map`` int32
+    [B,H,W] (0 background, k + 1 where ROI k owns the pixel), composed from the instance masks after
+    ``instance_post`` through the composer's pack front end, at the composer's frame size or, when it has none, the
+    images'.  Not part of a traced export either.
     """
 
     def __init__(self, model: HierarchicalRGBSegmentationModelWithFullImagePretrainedUNet, image_size=None,
-                 dilation_pixels: int = 0, binary_post=None, instance_post=None):
+                 dilation_pixels: int = 0, binary_post=None, instance_post=None, compose=None):
         super().__init__()
         self.model = model
         self.image_size = image_size
         self.dilation_pixels = dilation_pixels
         self.binary_post = binary_post
         self.instance_post = instance_post
+        self.compose = compose
+
+    def compose_map(self, inst: torch.Tensor, images: torch.Tensor, rois: torch.Tensor) -> torch.Tensor:
+        """instance_map of the (post-filtered) instance masks, on the current stream."""
+        from . import ops
+        c = self.compose
+        fs = c.resolve_frame_size((images.shape[0],)) if c.frame_size else (images.shape[0], *images.shape[-2:])
+        bits, score, _ = ops.roi_mask_pack(inst)
+        return ops.compose_instance_map(bits, score, rois, fs, inst.shape[-1])
 
     def forward(self, images: torch.Tensor, rois: torch.Tensor):
         H, W = images.shape[-2:] if self.image_size is None else self.image_size
@@ -231,16 +245,18 @@ class RGBHierarchicalExportWrapper(nn.Module):
             m.spatial_scale = (H, W)
             m.spatial_scale_h, m.spatial_scale_w = H, W
         if export.tracing(images, rois):
-            for hook in ("binary_post", "instance_post"):
+            for hook in ("binary_post", "instance_post", "compose"):
                 if getattr(self, hook) is not None:
-                    raise NotImplementedError(f"{hook} is set: the mask post-processing ops have no traced form; "
-                                              "export the wrapper without it")
+                    raise NotImplementedError(f"{hook} is set: the mask post-processing and instance composition ops "
+                                              "have no traced form; export the wrapper without it")
             return export.traced_export(self, images, rois)
         inst, binary = engine.export_forward(self.model, images, rois, self.dilation_pixels)
         if self.instance_post is not None:
             inst = self.instance_post(inst)
         if self.binary_post is not None:
             binary = self.binary_post(binary)
+        if self.compose is not None:
+            return inst, binary, self.compose_map(inst, images, rois)
         return inst, binary
 
 
@@ -314,12 +330,13 @@ class StreamPipelinedExport:
                 inst = engine.export_head_phase(w.model, images, rois, u, w.dilation_pixels)
                 if w.instance_post is not None:
                     inst = w.instance_post(inst)
-            outs.append((inst, binary))
+                imap = (w.compose_map(inst, images, rois),) if w.compose is not None else ()
+            outs.append((inst, binary) + imap)
         caller.wait_stream(self.s_unet)
         caller.wait_stream(self.s_head)
-        for inst, binary in outs:
-            inst.record_stream(caller)
-            binary.record_stream(caller)
+        for out in outs:
+            for t in out:
+                t.record_stream(caller)
         return outs
 
     def _set_scale(self, images):
@@ -369,16 +386,17 @@ class StreamPipelinedExport:
                     ops.GATE = None
                 if w.instance_post is not None:
                     inst = w.instance_post(inst)
-            outs.append((inst, binary))
+                imap = (w.compose_map(inst, images, rois),) if w.compose is not None else ()
+            outs.append((inst, binary) + imap)
             if nxt is not None:
                 u, binary = g.finish()
             if self._windows is None:
                 self._windows = g.counts + [0]
         caller.wait_stream(self.s_unet)
         caller.wait_stream(self.s_head)
-        for inst, binary in outs:
-            inst.record_stream(caller)
-            binary.record_stream(caller)
+        for out in outs:
+            for t in out:
+                t.record_stream(caller)
         return outs
 
 

@@ -926,3 +926,84 @@ def boundary_weight_map(mask: torch.Tensor, boundary_width: int = 5, boundary_we
     if squeeze:
         w, d2 = w[0], d2[0]
     return w, d2
+
+
+# ------------------------------------------------------------ full-frame instance composition (include/hiseg_compose.h)
+def _roi_bits(src: torch.Tensor, channels: int, what: str):
+    _require_gpu(src)
+    if src.dim() != 4 or src.shape[1] != channels:
+        raise ValueError(f"{what}: expected [N,{channels},mh,mw], got shape {tuple(src.shape)}")
+    src = src.to(torch.float32).contiguous()
+    N, _, mh, mw = src.shape
+    wpr = L.lib().hiseg_compose_words_per_row(mw)
+    bits = torch.empty(N, mh, wpr, dtype=torch.int32, device=src.device)
+    score = torch.empty(N, dtype=torch.float32, device=src.device)
+    count = torch.empty(N, dtype=torch.int32, device=src.device)
+    return src, N, mh, mw, bits, score, count
+
+
+def roi_mask_classify(logits: torch.Tensor, score_threshold: float = 0.5):
+    """Logits f32 [N,3,mh,mw] -> (bits int32 [N,mh,(mw+31)//32], score f32 [N], count int32 [N]): the target mask
+    (first-maximum argmax == 1 and softmax maximum > score_threshold) bit-packed, its mean confidence and its size."""
+    x, N, mh, mw, bits, score, count = _roi_bits(logits, 3, "roi_mask_classify")
+    L.check(L.lib().hiseg_roi_mask_classify_fwd(_ptr(x) if N else None, N, mh, mw, float(score_threshold),
+                                                bits.data_ptr(), score.data_ptr(), count.data_ptr(), L.stream_ptr()),
+            "roi_mask_classify")
+    return bits, score, count
+
+
+def roi_mask_pack(masks: torch.Tensor):
+    """instance_masks f32 [N,1,mh,mw] -> (bits, score, count) as roi_mask_classify: set where > 0.5, score 1 where
+    any pixel is set, else 0."""
+    x, N, mh, mw, bits, score, count = _roi_bits(masks, 1, "roi_mask_pack")
+    L.check(L.lib().hiseg_roi_mask_pack_fwd(_ptr(x) if N else None, N, mh, mw, bits.data_ptr(), score.data_ptr(),
+                                            count.data_ptr(), L.stream_ptr()), "roi_mask_pack")
+    return bits, score, count
+
+
+def compose_instance_map(bits: torch.Tensor, score: torch.Tensor, rois: torch.Tensor, frame_size, mask_width: int):
+    """Packed masks, scores and rois f32 [N,5] -> label int32 [B,H,W] for frame_size = (B, H, W): 0 is background,
+    k + 1 means ROI k owns the pixel (the highest ROI index of the frame whose nearest-resized mask is set there)."""
+    _require_gpu(bits, score, rois)
+    B, H, W = (int(v) for v in frame_size)
+    if bits.dim() != 3 or bits.dtype != torch.int32:
+        raise ValueError(f"compose_instance_map: expected int32 bits [N,mh,words], got {bits.dtype} "
+                         f"{tuple(bits.shape)}")
+    N, mh, wpr = bits.shape
+    mw = int(mask_width)
+    if wpr != L.lib().hiseg_compose_words_per_row(mw):
+        raise ValueError(f"compose_instance_map: {wpr} words per row do not hold a mask {mw} wide")
+    if tuple(rois.shape) != (N, 5) or tuple(score.shape) != (N,):
+        raise ValueError(f"compose_instance_map: {N} masks, rois {tuple(rois.shape)}, score {tuple(score.shape)}")
+    bits, score = bits.contiguous(), score.to(torch.float32).contiguous()
+    rois = rois.to(torch.float32).contiguous()
+    label = torch.empty(B, H, W, dtype=torch.int32, device=bits.device)
+    L.check(L.lib().hiseg_instance_map_fwd(_ptr(bits) if N else None, _ptr(score) if N else None,
+                                           _ptr(rois) if N else None, N, mh, mw, B, H, W, label.data_ptr(),
+                                           L.stream_ptr()), "instance_map")
+    return label
+
+
+def instance_overlay(label: torch.Tensor, image: torch.Tensor, colors: torch.Tensor, alpha: float = 0.5):
+    """label int32 [B,H,W], image uint8 [B,H,W,3], colors uint8 [N,3] -> uint8 [B,H,W,3]: cv2.addWeighted(image,
+    1 - alpha, colour of the owner (0 where there is none), alpha, 0)."""
+    _require_gpu(label, image, colors)
+    if label.dim() != 3 or label.dtype != torch.int32:
+        raise ValueError(f"instance_overlay: expected an int32 label map [B,H,W], got {label.dtype} "
+                         f"{tuple(label.shape)}")
+    B, H, W = label.shape
+    if tuple(image.shape) != (B, H, W, 3) or image.dtype != torch.uint8:
+        raise ValueError(f"instance_overlay: expected a uint8 image {(B, H, W, 3)}, got {image.dtype} "
+                         f"{tuple(image.shape)}")
+    if colors.dim() != 2 or colors.shape[1] != 3 or colors.dtype != torch.uint8:
+        raise ValueError(f"instance_overlay: expected uint8 colors [N,3], got {colors.dtype} {tuple(colors.shape)}")
+    label, image, colors = label.contiguous(), image.contiguous(), colors.contiguous()
+    if label.data_ptr() % 16:    # a view into a larger buffer: the kernel reads labels four to a 16-byte load
+        label = label.clone()
+    if image.data_ptr() % 4:
+        image = image.clone()
+    N = colors.shape[0]
+    out = torch.empty_like(image)
+    L.check(L.lib().hiseg_instance_overlay_fwd(label.data_ptr(), image.data_ptr(), _ptr(colors) if N else None, N, B,
+                                               H, W, float(alpha), out.data_ptr(), L.stream_ptr()), "instance_overlay")
+    return out
