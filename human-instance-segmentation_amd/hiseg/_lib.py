@@ -407,6 +407,10 @@ def _declare(lib):
         "hiseg_roi_mask_pack_fwd": ([P, c_ll, c_int, c_int, P, P, P, P], c_int),
         "hiseg_instance_map_fwd": ([P, P, P, c_ll, c_int, c_int, c_int, c_int, c_int, P, P], c_int),
         "hiseg_instance_overlay_fwd": ([P, P, P, c_ll, c_int, c_int, c_int, ctypes.c_double, P, P], c_int),
+        # ---- ROI-model knowledge distillation (include/hiseg_kd.h)
+        "hiseg_kd_ws": ([c_int, c_int, c_int], c_ll),
+        "hiseg_kd_loss_fwd": ([P, P, P, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P], c_int),
+        "hiseg_kd_loss_bwd": ([P, P, P, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P, P, P], c_int),
         "hiseg_optim_blocks": ([], c_int),
         "hiseg_grad_norm_partials": ([P, c_ll, P, P], c_int),
         "hiseg_adamw_step": ([P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_float, c_float, c_float, P,
