@@ -1468,6 +1468,8 @@ extern "C" int hiseg_act_bwd_cvt(int dtype, long long P, int C, hiseg_ew_view dy
                                  hiseg_ew_view dz, int accumulate, hiseg_stream_t stream) {
   HISEG_REQUIRE(dy.p && dz.p && P > 0 && C > 0 && (act == HISEG_ACT_NONE || y.p), HISEG_ERR_BAD_ARG,
                 "act_bwd_cvt: bad arguments");
+  // the derivative is taken from the OUTPUT y: SiLU / GELU / Swish are not functions of it (act_bwd_pre takes them)
+  HISEG_REQUIRE(!act_smooth(act), HISEG_ERR_BAD_ARG, "act_bwd_cvt: a smooth activation needs its pre-activation");
   DISPATCH_T(dtype, hipLaunchKernelGGL(act_bwd_cvt_kernel<T>, dim3(ew_blocks(P * C)), dim3(256), 0, (hipStream_t)stream,
                                        P, C, dy, y, act, dz, accumulate));
   return hiseg_check_launch("act_bwd_cvt");

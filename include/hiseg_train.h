@@ -208,7 +208,8 @@ int hiseg_gate_fwd(int dtype, long long P, int C, hiseg_ew_view a, hiseg_ew_view
 int hiseg_gate_bwd(int dtype, long long P, int C, hiseg_ew_view dy, hiseg_ew_view a, hiseg_ew_view g,
                    hiseg_ew_view da, int da_accumulate, hiseg_ew_view dzg, hiseg_stream_t stream);
 /* dz (dtype, += if accumulate) = dy * act'(y) with dy, y f32 views (the 1/2-channel f32 heads:
- * contour sigmoid, distance map, EnhancedUNet's f32 logits). act: NONE or SIGMOID (y = output). */
+ * contour sigmoid, distance map, EnhancedUNet's f32 logits). act: NONE, RELU or SIGMOID (y = output); SiLU / GELU /
+ * Swish are not functions of their output and return HISEG_ERR_BAD_ARG (hiseg_act_bwd_pre takes them). */
 int hiseg_act_bwd_cvt(int dtype, long long P, int C, hiseg_ew_view dy, hiseg_ew_view y, int act, hiseg_ew_view dz,
                       int accumulate, hiseg_stream_t stream);
 int hiseg_add_inplace(int dtype, long long P, int C, hiseg_ew_view dst, hiseg_ew_view src, hiseg_stream_t stream);
