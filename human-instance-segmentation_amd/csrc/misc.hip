@@ -1099,7 +1099,7 @@ extern "C" int hiseg_maxpool2x2_fwd(int dtype, const void* in, int N, int H, int
 
 extern "C" int hiseg_attn_spatial_fwd(int dtype, const void* x, int N, int H, int W, int C, const float* w7, int k,
                                       float* stats, float* att, void* out, hiseg_stream_t stream) {
-  HISEG_REQUIRE(x && w7 && stats && att && out && N > 0 && H > 0 && W > 0 && C > 0 && (k & 1), HISEG_ERR_BAD_ARG,
+  HISEG_REQUIRE(x && w7 && stats && att && out && N > 0 && H > 0 && W > 0 && C > 0 && k > 0 && (k & 1), HISEG_ERR_BAD_ARG,
                 "attn_spatial: bad args");
   HISEG_REQUIRE(C % chunk_of(dtype) == 0, HISEG_ERR_BAD_SHAPE, "attn_spatial: C must be chunk aligned");
   hipStream_t s = (hipStream_t)stream;
@@ -1113,7 +1113,7 @@ extern "C" int hiseg_attn_spatial_fwd(int dtype, const void* x, int N, int H, in
 
 extern "C" int hiseg_attn_map_fwd(int dtype, const void* x, int N, int H, int W, int C, const float* w7, int k,
                                   float* stats, float* att, hiseg_stream_t stream) {
-  HISEG_REQUIRE(x && w7 && stats && att && N > 0 && H > 0 && W > 0 && C > 0 && (k & 1), HISEG_ERR_BAD_ARG,
+  HISEG_REQUIRE(x && w7 && stats && att && N > 0 && H > 0 && W > 0 && C > 0 && k > 0 && (k & 1), HISEG_ERR_BAD_ARG,
                 "attn_map: bad args");
   HISEG_REQUIRE(C % chunk_of(dtype) == 0, HISEG_ERR_BAD_SHAPE, "attn_map: C must be chunk aligned");
   hipStream_t s = (hipStream_t)stream;
@@ -1167,7 +1167,9 @@ extern "C" int hiseg_se_gate_fwd(int dtype, const void* x, int N, int HW, int C,
 
 extern "C" int hiseg_channel_scale_fwd(int dtype, const void* x, int N, int HW, int C, const float* gate, void* out,
                                        hiseg_stream_t stream) {
-  HISEG_REQUIRE(x && gate && out && N > 0 && HW > 0 && C % chunk_of(dtype) == 0, HISEG_ERR_BAD_ARG, "channel_scale: bad args");
+  // C > 0: C = 0 passed the chunk test and reached a zero-block launch
+  HISEG_REQUIRE(x && gate && out && N > 0 && HW > 0 && C > 0 && C % chunk_of(dtype) == 0, HISEG_ERR_BAD_ARG,
+                "channel_scale: bad args");
   const long long total = (long long)N * HW * (C / chunk_of(dtype));
   DISPATCH_T(dtype, channel_scale_kernel, dim3(nblocks(total, 256)), dim3(256), 0, (hipStream_t)stream, x, N, (long long)HW,
              C, gate, out);
@@ -1386,7 +1388,8 @@ extern "C" int hiseg_image_max_fwd(const float* x, long long n, float* maxbuf, h
 
 extern "C" int hiseg_input_norm_fwd(int dtype, const float* x, int B, int C, int H, int W, const float* maxbuf,
                                     const float* mean, const float* stdv, void* out, int cpad, hiseg_stream_t stream) {
-  HISEG_REQUIRE(x && maxbuf && mean && stdv && out && B > 0 && C > 0 && cpad >= C, HISEG_ERR_BAD_ARG, "input_norm: bad args");
+  HISEG_REQUIRE(x && maxbuf && mean && stdv && out && B > 0 && C > 0 && H > 0 && W > 0 && cpad >= C, HISEG_ERR_BAD_ARG,
+                "input_norm: bad args");
   const long long total = (long long)B * H * W;
   DISPATCH_T(dtype, input_norm_kernel, dim3(nblocks(total, 256)), dim3(256), 0, (hipStream_t)stream, x, B, C, H, W,
              reinterpret_cast<const unsigned*>(maxbuf), mean, stdv, out, cpad);
@@ -1488,7 +1491,9 @@ extern "C" int hiseg_ubf_ln_tables(const float* low, int N, int h, int w, const 
 
 extern "C" int hiseg_nhwc_to_nchw_fwd(int dtype, const void* in, int N, int H, int W, int C, int cstride, int coff, float* out,
                                       hiseg_stream_t stream) {
-  HISEG_REQUIRE(in && out && N >= 0 && C > 0 && cstride >= coff + C, HISEG_ERR_BAD_ARG, "nhwc_to_nchw: bad args");
+  // coff >= 0: a negative offset satisfied cstride >= coff + C and read in front of the buffer
+  HISEG_REQUIRE(in && out && N >= 0 && H >= 0 && W >= 0 && C > 0 && coff >= 0 && cstride >= coff + C, HISEG_ERR_BAD_ARG,
+                "nhwc_to_nchw: bad args");
   const long long total = (long long)N * C * H * W;
   if (total == 0) return HISEG_OK;
   DISPATCH_T(dtype, nhwc_to_nchw_kernel, dim3(nblocks(total, 256)), dim3(256), 0, (hipStream_t)stream, in, N, H, W, C, cstride,
@@ -1498,7 +1503,7 @@ extern "C" int hiseg_nhwc_to_nchw_fwd(int dtype, const void* in, int N, int H, i
 
 extern "C" int hiseg_nchw_to_nhwc_fwd(int dtype, const float* in, int N, int C, int H, int W, void* out, int cpad,
                                       hiseg_stream_t stream) {
-  HISEG_REQUIRE(in && out && N >= 0 && C > 0 && cpad >= C, HISEG_ERR_BAD_ARG, "nchw_to_nhwc: bad args");
+  HISEG_REQUIRE(in && out && N >= 0 && H >= 0 && W >= 0 && C > 0 && cpad >= C, HISEG_ERR_BAD_ARG, "nchw_to_nhwc: bad args");
   const long long total = (long long)N * H * W;
   if (total == 0) return HISEG_OK;
   DISPATCH_T(dtype, nchw_to_nhwc_kernel, dim3(nblocks(total, 256)), dim3(256), 0, (hipStream_t)stream, in, N, C, H, W, out, cpad);
@@ -1518,7 +1523,8 @@ extern "C" int hiseg_instance_masks_fwd(const float* logits, int N, int mh, int 
 extern "C" int hiseg_binary_masks_fwd(int dtype, const void* u, int u_cstride, int B, int H, int W, const float* oc_w,
                                       const float* oc_b, float* binary, hiseg_stream_t stream) {
   HISEG_REQUIRE(dtype == HISEG_F32, HISEG_ERR_BAD_DTYPE, "binary_masks: the UNet logit map is f32");
-  HISEG_REQUIRE(u && oc_w && oc_b && binary && B > 0 && u_cstride >= 1, HISEG_ERR_BAD_ARG, "binary_masks: bad args");
+  HISEG_REQUIRE(u && oc_w && oc_b && binary && B > 0 && H > 0 && W > 0 && u_cstride >= 1, HISEG_ERR_BAD_ARG,
+                "binary_masks: bad args");
   const long long P = (long long)B * H * W;
   hipLaunchKernelGGL(binary_mask_kernel, dim3(nblocks(P, 256)), dim3(256), 0, (hipStream_t)stream,
                      reinterpret_cast<const float*>(u), u_cstride, P, oc_w, oc_b, binary);

@@ -256,8 +256,13 @@ int hiseg_se_gate_partials_fwd(float* partial, int splits, int N, int HW, int C,
 /* Image prologue of PreTrainedPeopleSegmentationUNet.normalize_input
  * (hierarchical_segmentation_unet.py:1885-1890) fused with NCHW f32 -> NHWC(dtype, C padded
  * to cpad) conversion.  The reference's host-synchronising `if x.max() > 1: x /= 255` is a
- * device-side flag: hiseg_image_max_fwd writes max(x) to *maxbuf (one float, caller
- * zero-initialises nothing: the call resets it), the normalize kernel reads it. */
+ * device-side flag: hiseg_image_max_fwd leaves max(x) in *maxbuf (4 bytes, caller
+ * zero-initialises nothing: the call resets it), the normalize kernel reads it.  *maxbuf is NOT the float:
+ * it holds the maximum's order-preserving unsigned key (sign bit set for x >= +0, all bits flipped for
+ * negative x; -0.0 sorts below +0.0), which only hiseg_input_norm_fwd decodes.
+ * Argument checks added with the per-kernel inference tests: hiseg_input_norm_fwd, hiseg_binary_masks_fwd
+ * require H, W > 0; hiseg_channel_scale_fwd C > 0; hiseg_nhwc_to_nchw_fwd coff >= 0; the layout converters
+ * H, W >= 0; the attention entry points k > 0 (an empty grid or an out-of-range read otherwise). */
 int hiseg_image_max_fwd(const float* x, long long n, float* maxbuf, hiseg_stream_t stream);
 int hiseg_input_norm_fwd(int dtype, const float* x, int B, int C, int H, int W, const float* maxbuf,
                          const float* mean, const float* std, void* out, int cpad,
