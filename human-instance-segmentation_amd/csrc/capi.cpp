@@ -8,6 +8,7 @@
 #include "hiseg.h"
 #include "hiseg_data.h"
 #include "hiseg_distill.h"
+#include "hiseg_guided_head.h"
 #include "hiseg_head_train.h"
 #include "hiseg_loss.h"
 #include "hiseg_train.h"
@@ -66,6 +67,14 @@ extern "C" int hiseg_struct_sizes(long long* out, int n) {
                           (long long)sizeof(hiseg_ubf_desc),       (long long)sizeof(hiseg_ubf_grads),
                           (long long)sizeof(hiseg_loss_cfg),       (long long)sizeof(hiseg_distill_cfg),
                           (long long)sizeof(hiseg_roi_target_desc)};
+  const int m = (int)(sizeof(sz) / sizeof(sz[0]));
+  for (int i = 0; i < n && i < m; ++i) out[i] = sz[i];
+  return m;
+}
+
+extern "C" int hiseg_guided_struct_sizes(long long* out, int n) {
+  const long long sz[] = {(long long)sizeof(hiseg_guided_prep_desc), (long long)sizeof(hiseg_guided_attn_desc),
+                          (long long)sizeof(hiseg_guided_finish_desc)};
   const int m = (int)(sizeof(sz) / sizeof(sz[0]));
   for (int i = 0; i < n && i < m; ++i) out[i] = sz[i];
   return m;

@@ -7,8 +7,8 @@ every forward runs on libhiseg (hand-written gfx950 HIP kernels, C ABI in includ
 """
 from .layers import (  # noqa: F401
     BoundaryRefinementModule, ChannelAttentionModule, ContourDetectionBranch, DistanceTransformDecoder, EnhancedUNet,
-    ExtendedHierarchicalSegmentationHeadUNetV2, LayerNorm2d, RefinedHierarchicalSegmentationHead, ResidualBlock,
-    SpatialAttentionModule)
+    ExtendedHierarchicalSegmentationHeadUNetV2, LayerNorm2d, PretrainedUNetGuidedSegmentationHead,
+    RefinedHierarchicalSegmentationHead, ResidualBlock, SpatialAttentionModule)
 from .effunet import EfficientNetUnet  # noqa: F401
 from .model import (  # noqa: F401
     DynamicRoIAlign, HierarchicalRGBSegmentationModelWithFullImagePretrainedUNet, PreTrainedPeopleSegmentationUNet,

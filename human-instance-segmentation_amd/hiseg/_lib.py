@@ -245,6 +245,29 @@ class RoiTargetDesc(ctypes.Structure):
                                                                  "y2", "img_w", "img_h")]
 
 
+class GuidedPrepDesc(Desc):
+    """include/hiseg_guided_head.h hiseg_guided_prep_desc"""
+    _fields_ = [("mask", c_void_p), ("mask_stride", c_ll), ("N", c_int), ("h", c_int), ("w", c_int), ("dtype", c_int),
+                ("fgp_c", c_void_p), ("fgp_cstride", c_int), ("fgp_coff", c_int),
+                ("fg_prob", c_void_p), ("factor", c_void_p)]
+
+
+class GuidedAttnDesc(Desc):
+    """include/hiseg_guided_head.h hiseg_guided_attn_desc"""
+    _fields_ = [("dtype", c_int), ("x", c_void_p), ("P", c_ll), ("C", c_int), ("hidden", c_int),
+                ("w1t", c_void_p), ("b1", c_void_p), ("w2", c_void_p), ("b2", c_void_p),
+                ("act", c_int), ("act_beta", c_float),
+                ("factor", c_void_p), ("att", c_void_p), ("gate", c_void_p), ("w1_frag", c_void_p)]
+
+
+class GuidedFinishDesc(Desc):
+    """include/hiseg_guided_head.h hiseg_guided_finish_desc"""
+    _fields_ = [("dtype", c_int), ("z", c_void_p), ("N", c_int), ("h", c_int), ("w", c_int), ("C", c_int),
+                ("w3", c_void_p), ("b3", c_void_p), ("mh", c_int), ("mw", c_int), ("logits", c_void_p),
+                ("mask", c_void_p), ("mask_stride", c_ll),
+                ("bg_fg_logits", c_void_p), ("fg_prob", c_void_p), ("mask_out", c_void_p), ("tn_logits", c_void_p)]
+
+
 class HisegError(RuntimeError):
     """Raised when a libhiseg entry point returns a non-zero status."""
 
@@ -411,6 +434,12 @@ def _declare(lib):
         "hiseg_kd_ws": ([c_int, c_int, c_int], c_ll),
         "hiseg_kd_loss_fwd": ([P, P, P, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P], c_int),
         "hiseg_kd_loss_bwd": ([P, P, P, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P, P, P], c_int),
+        # ---- UNet-guided direct 3-class head (include/hiseg_guided_head.h)
+        "hiseg_guided_struct_sizes": ([ctypes.POINTER(c_ll), c_int], c_int),
+        "hiseg_guided_prep_fwd": ([ctypes.POINTER(GuidedPrepDesc), P], c_int),
+        "hiseg_guided_attn_fwd": ([ctypes.POINTER(GuidedAttnDesc), P], c_int),
+        "hiseg_guided_finish_rows": ([c_int, c_int, c_int, c_int], c_int),
+        "hiseg_guided_finish_fwd": ([ctypes.POINTER(GuidedFinishDesc), P], c_int),
         "hiseg_optim_blocks": ([], c_int),
         "hiseg_grad_norm_partials": ([P, c_ll, P, P], c_int),
         "hiseg_adamw_step": ([P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_float, c_float, c_float, P,

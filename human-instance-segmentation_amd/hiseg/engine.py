@@ -195,15 +195,15 @@ def residual_block(E: Ctx, blk: nn.Module, x: Act, out: Optional[Act] = None,
     return cna(E, blk.conv2, blk.norm2, a2, h, residual=x, out=out)
 
 
-def rgb_feature_extractor(E: Ctx, seq: nn.Sequential, x: Act) -> Act:
-    """hierarchical_segmentation_rgb.py:657-673."""
+def rgb_feature_extractor(E: Ctx, seq: nn.Sequential, x: Act, out: Optional[Act] = None) -> Act:
+    """hierarchical_segmentation_rgb.py:657-673.  ``out``: where the last layer writes."""
     h = cna(E, seq[0], seq[1], act_code(seq[2]), x)
     h = residual_block(E, seq[3], h)
     h = cna(E, seq[4], seq[5], act_code(seq[6]), h)
     h = residual_block(E, seq[7], h)
     h = cna(E, seq[8], seq[9], act_code(seq[10]), h)
     h = residual_block(E, seq[11], h)
-    return cna(E, seq[12], seq[13], act_code(seq[14]), h)
+    return cna(E, seq[12], seq[13], act_code(seq[14]), h, out=out)
 
 
 def enhanced_unet(E: Ctx, u: nn.Module, x: Act) -> Tuple[Act, Act]:
@@ -343,6 +343,68 @@ def hier_head(E: Ctx, head: nn.Module, feat: Act, aux: str) -> Tuple[torch.Tenso
                                             dmask.data_ptr(), L.stream_ptr()), "distance_mask")
         auxd["distance_mask"] = _resize(dmask, mh, mw, lib)
         auxd["distance_map"] = _resize(dmap, mh, mw, lib)
+    return logits, auxd
+
+
+# A/B switches of the guided head's fused forms (tests, tools/guided_head_bench.py): False takes the explicit
+# fall-back -- a materialised 257-channel input_adjust input / a pixel_scale pass before final_classifier.0.
+GUIDED_FUSE_SRC_B = True
+GUIDED_FUSE_PX_SCALE = True
+
+
+def guided_head(E: Ctx, head: nn.Module, feats: Act, mask: torch.Tensor, aux: str, feats_into=None):
+    """PretrainedUNetGuidedSegmentationHead.forward (rgb.py:123-218), eval mode.  ``mask``: f32 [N, 1 or 2, h, w],
+    the raw foreground logit in its last channel, at the features' size.  ``feats_into``: the explicit fall-back of
+    the source-B form -- a callable taking the 256-channel slice of the 257-channel buffer and writing the features
+    there (``feats`` is then None)."""
+    if head.training:
+        raise NotImplementedError("PretrainedUNetGuidedSegmentationHead is inference only on the hiseg path; "
+                                  "call .eval()")
+    want = aux == "full"
+    att_on = head.use_attention_module
+    N, _, h, w = mask.shape
+    mh, mw = head.mask_height, head.mask_width
+    same = (mh, mw) == (h, w)
+    ia = head.input_adjust
+    cin = ia.in_channels - 1
+    if feats_into is None:   # fg_prob is loader source B of input_adjust: the 257-channel tensor never exists
+        assert (feats.N, feats.H, feats.W, feats.C) == (N, h, w, cin), "features and mask sizes differ"
+        fgp, fg_low, factor = ops.guided_prep(mask, E.dtype, want_fg_prob=want and same, want_factor=att_on)
+        x = ops.conv2d(E.conv(ia, split=(cin, 1)), feats, fgp)
+    else:
+        comb = Act.new(N, h, w, cin + 1, E.dtype, E.device, zero=False)
+        feats_into(comb.slice(0, cin))
+        _, fg_low, factor = ops.guided_prep(mask, E.dtype, out=comb.slice(cin, 1), want_fg_prob=want and same,
+                                            want_factor=att_on)
+        x = ops.conv2d(E.conv(ia), comb)
+    fp = head.feature_processor
+    y = cna(E, fp[0], fp[1], act_code(fp[2]), x)
+    y = residual_block(E, fp[4], y)
+    y = residual_block(E, fp[6], y)
+    fc = head.final_classifier
+    att = None
+    if att_on:
+        am = head.attention_module
+        if am[0].out_channels != 64 or am[0].in_channels != y.C:
+            raise NotImplementedError(f"the guided head's attention kernel is built for 64 hidden units "
+                                      f"(mid_channels 256), got {am[0].out_channels}")
+        w1t, frag = E._get(("guided_attn", id(am[0])), lambda: ops.pack_guided_attn(am[0].weight, E.dtype, E.device),
+                           (am[0].weight,))
+        gate, att = ops.guided_attn(y, w1t, E.f32(am[0].bias), E.f32(am[2].weight, (64,)), E.f32(am[2].bias),
+                                    act_code(am[1]), factor, want_att=want, w1_frag=frag)
+        if isinstance(fc[1], LayerNorm2d) or not GUIDED_FUSE_PX_SCALE:
+            z = cna(E, fc[0], fc[1], act_code(fc[2]), ops.pixel_scale(y, gate))
+        else:   # the gate multiply rides in final_classifier.0's loader where the layer has that form
+            z = ops.conv2d(E.conv(fc[0], fc[1], act_code(fc[2])), y, px_scale=gate)
+    else:
+        z = cna(E, fc[0], fc[1], act_code(fc[2]), y)
+    logits, auxd = ops.guided_finish(z, E.f32(fc[3].weight, (3, fc[3].in_channels)), E.f32(fc[3].bias), mh, mw,
+                                     mask=mask, want_aux=want, want_fg_prob=not same)
+    if not want:
+        return logits, {}
+    if same:   # nothing is resized: fg_prob is the ROI-size one (rgb.py:143, :187-194)
+        auxd["fg_prob"] = fg_low
+    auxd["attention"] = att.view(N, 1, h, w) if att is not None else None
     return logits, auxd
 
 
@@ -557,20 +619,35 @@ def rgb_model_forward(model: nn.Module, images: torch.Tensor, rois: torch.Tensor
         u = unet_logit(E, wrapper.model, images)
     oc = wrapper.output_conv
     ma, mr = model.roi_align_mask, model.roi_align_rgb
-    roi_logits = Act.new(N, rh, rw, 2, E.dtype, dev, zero=False)
-    ops.roi_align(u, rois, rh, rw, ma.spatial_scale_h, ma.spatial_scale_w, ma.aligned, out=roi_logits,
-                  aff_w=E.f32(oc.weight, (2,)), aff_b=E.f32(oc.bias), zero_to=roi_logits.cstride)
-    rgb = Act.new(N, rh, rw, 3, E.dtype, dev, zero=False)
-    ops.roi_align(images, rois, rh, rw, mr.spatial_scale_h, mr.spatial_scale_w, mr.aligned, out=rgb,
-                  zero_to=rgb.cstride)
-    feats = rgb_feature_extractor(E, model.rgb_feature_extractor, rgb)
-    comb = ops.conv2d(E.conv(model.feature_combiner, split=(feats.C, 2)), feats, roi_logits)
-    logits, auxd = hier_head(E, model.segmentation_head, comb, aux)
-    if aux == "full":
-        auxd["full_image_logits"] = _output_conv(E, oc, u)
+    guided = not hasattr(model, "feature_combiner")   # rgb.py:758-765: the guided head takes features and masks
+    rf = None
+    if guided:   # the guidance is read in f32 whatever the compute dtype: its aux tensors saturate (rgb.py:196-202)
         rf = torch.empty(N, 2, rh, rw, dtype=torch.float32, device=dev)
         ops.roi_align(u, rois, rh, rw, ma.spatial_scale_h, ma.spatial_scale_w, ma.aligned, nchw_out=rf,
                       aff_w=E.f32(oc.weight, (2,)), aff_b=E.f32(oc.bias))
+    else:
+        roi_logits = Act.new(N, rh, rw, 2, E.dtype, dev, zero=False)
+        ops.roi_align(u, rois, rh, rw, ma.spatial_scale_h, ma.spatial_scale_w, ma.aligned, out=roi_logits,
+                      aff_w=E.f32(oc.weight, (2,)), aff_b=E.f32(oc.bias), zero_to=roi_logits.cstride)
+    rgb = Act.new(N, rh, rw, 3, E.dtype, dev, zero=False)
+    ops.roi_align(images, rois, rh, rw, mr.spatial_scale_h, mr.spatial_scale_w, mr.aligned, out=rgb,
+                  zero_to=rgb.cstride)
+    if guided and not GUIDED_FUSE_SRC_B:
+        logits, auxd = guided_head(E, model.segmentation_head, None, rf, aux, feats_into=lambda dst: (
+            rgb_feature_extractor(E, model.rgb_feature_extractor, rgb, out=dst)))
+    elif guided:
+        feats = rgb_feature_extractor(E, model.rgb_feature_extractor, rgb)
+        logits, auxd = guided_head(E, model.segmentation_head, feats, rf, aux)
+    else:
+        feats = rgb_feature_extractor(E, model.rgb_feature_extractor, rgb)
+        comb = ops.conv2d(E.conv(model.feature_combiner, split=(feats.C, 2)), feats, roi_logits)
+        logits, auxd = hier_head(E, model.segmentation_head, comb, aux)
+    if aux == "full":
+        auxd["full_image_logits"] = _output_conv(E, oc, u)
+        if rf is None:
+            rf = torch.empty(N, 2, rh, rw, dtype=torch.float32, device=dev)
+            ops.roi_align(u, rois, rh, rw, ma.spatial_scale_h, ma.spatial_scale_w, ma.aligned, nchw_out=rf,
+                          aff_w=E.f32(oc.weight, (2,)), aff_b=E.f32(oc.bias))
         auxd["roi_features"] = rf
         rp = torch.empty(N, 3, rh, rw, dtype=torch.float32, device=dev)
         ops.roi_align(images, rois, rh, rw, mr.spatial_scale_h, mr.spatial_scale_w, mr.aligned, nchw_out=rp)
@@ -632,6 +709,29 @@ def boundary_refine_nchw(mod: nn.Module, x: torch.Tensor, want_edges: bool = Fal
     _check_input(x, "BoundaryRefinementModule")
     E = Ctx(mod, _root_dtype(mod), x.device)
     return boundary_refine(E, mod, x, want_edges)
+
+
+def guided_head_nchw(head: nn.Module, features: torch.Tensor, bg_fg_mask: torch.Tensor):
+    _check_input(features, "PretrainedUNetGuidedSegmentationHead")
+    _check_input(bg_fg_mask, "PretrainedUNetGuidedSegmentationHead")
+    if bg_fg_mask.dim() != 4 or bg_fg_mask.shape[1] not in (1, 2) or bg_fg_mask.shape[0] != features.shape[0]:
+        raise ValueError(f"bg_fg_mask: expected [N, 1 or 2, h, w], got shape {tuple(bg_fg_mask.shape)}")
+    if tuple(bg_fg_mask.shape[2:]) != tuple(features.shape[2:]):
+        raise NotImplementedError(
+            f"bg_fg_mask {tuple(bg_fg_mask.shape[2:])} and features {tuple(features.shape[2:])} differ in size: the "
+            "resize of fg_prob to the feature size (rgb.py:147-153) is not on the hiseg path (the model aligns both "
+            "to the ROI size)")
+    E = Ctx(head, _root_dtype(head), features.device)
+    mask = bg_fg_mask.to(torch.float32).contiguous()
+    if GUIDED_FUSE_SRC_B:
+        return guided_head(E, head, Act.from_nchw(features, E.dtype), mask, "full")
+    x = features.contiguous().float()
+
+    def into(dst: Act):
+        N, C, H, W = x.shape
+        L.check(L.lib().hiseg_nchw_to_nhwc_fwd(ops.hdtype(E.dtype), x.data_ptr(), N, C, H, W, dst.ptr(), dst.cstride,
+                                               L.stream_ptr()), "nchw_to_nhwc")
+    return guided_head(E, head, None, mask, "full", feats_into=into)
 
 
 def head_nchw(head: nn.Module, x: torch.Tensor):

@@ -284,7 +284,16 @@ def refuse_boundary_refiner(model: torch.nn.Module) -> None:
             "which the lowering does not express; export the masks with the eager path (export_forward)")
 
 
+def refuse_guided_head(model: torch.nn.Module) -> None:
+    if type(getattr(model, "segmentation_head", None)).__name__ == "PretrainedUNetGuidedSegmentationHead":
+        raise NotImplementedError(
+            "traced / torch.export / ONNX export of a model with the PretrainedUNetGuidedSegmentationHead (no "
+            "refinement flag) is not supported: the exported head op and its ONNX lowering describe the refined "
+            "head; serve this model with the eager path (RGBHierarchicalExportWrapper, StreamPipelinedExport)")
+
+
 def _head_spec(model: torch.nn.Module, aux: str) -> str:
+    refuse_guided_head(model)
     refuse_boundary_refiner(model)
     ma, mr = model.roi_align_mask, model.roi_align_rgb
     scales = [float(ma.spatial_scale_h), float(ma.spatial_scale_w)]
@@ -294,6 +303,7 @@ def _head_spec(model: torch.nn.Module, aux: str) -> str:
 
 
 def traced_rgb_model(model: torch.nn.Module, images: Tensor, rois: Tensor, aux: str = "full"):
+    refuse_guided_head(model)
     u = traced_unet_logit(model.pretrained_unet.model, images)
     outs = torch.ops.hiseg.rgb_head(images, u, rois, _state(model, UNET_PREFIX), _head_spec(model, aux))
     names = [n for n, _ in rgb_out_templates(model, aux)]
@@ -306,6 +316,7 @@ def traced_rgb_model(model: torch.nn.Module, images: Tensor, rois: Tensor, aux: 
 
 def traced_export(wrapper: torch.nn.Module, images: Tensor, rois: Tensor):
     model = wrapper.model
+    refuse_guided_head(model)
     u = traced_unet_logit(model.pretrained_unet.model, images)
     oc = model.pretrained_unet.output_conv
     binary = torch.ops.hiseg.binary_masks(u, oc.weight, oc.bias)

@@ -281,6 +281,50 @@ class ExtendedHierarchicalSegmentationHeadUNetV2(nn.Module):
             nn.Conv2d(m // 4, half, 1), make_act(act, beta), nn.Conv2d(half, m, 1), nn.Sigmoid())
 
 
+class PretrainedUNetGuidedSegmentationHead(nn.Module):
+    """Direct 3-class head guided by the full-image UNet's foreground logit --
+    advanced/hierarchical_segmentation_rgb.py:43-218.  The model's head when no refinement flag is set (:715-727).
+
+    ``forward(features, bg_fg_mask)``: features [N, in_channels, h, w], bg_fg_mask [N, 1 or 2, h, w] (the foreground
+    logit is the last channel) at the features' size.  Inference only: the eval-mode forward runs through
+    :func:`hiseg.engine.guided_head`; train mode raises."""
+
+    def __init__(self, in_channels: int, mid_channels: int = 256, num_classes: int = 3,
+                 mask_size: Union[int, Tuple[int, int]] = 56, dropout_rate: float = 0.1,
+                 use_attention_module: bool = False, normalization_type: str = "layernorm2d",
+                 normalization_groups: int = 8, activation_function: str = "relu", activation_beta: float = 1.0):
+        super().__init__()
+        assert num_classes == 3, "Hierarchical model designed for 3 classes"
+        self.num_classes = num_classes
+        self.mask_height, self.mask_width = _hw(mask_size)
+        self.use_attention_module = use_attention_module
+        norm, g, act, beta = normalization_type, normalization_groups, activation_function, activation_beta
+        m = mid_channels
+        self.input_adjust = nn.Conv2d(in_channels + 1, in_channels, 1)
+        # activations from rgb.py's own factory (:21-40: 'swish' is nn.SiLU), the blocks' from the refinement module's
+        self.feature_processor = nn.Sequential(
+            nn.Conv2d(in_channels, m, 3, padding=1), make_norm(norm, m, min(g, m)), make_act_unet(act, beta),
+            nn.Dropout2d(dropout_rate), ResidualBlock(m, norm, g, act, beta), nn.Dropout2d(dropout_rate),
+            ResidualBlock(m, norm, g, act, beta))
+        self.final_classifier = nn.Sequential(
+            nn.Conv2d(m, m // 2, 3, padding=1), make_norm(norm, m // 2, min(g, m // 2)), make_act_unet(act, beta),
+            nn.Conv2d(m // 2, num_classes, 1))
+        if use_attention_module:
+            self.attention_module = nn.Sequential(
+                nn.Conv2d(m, m // 4, 1), make_act_unet(act, beta), nn.Conv2d(m // 4, 1, 1), nn.Sigmoid())
+        with torch.no_grad():   # expected class distribution (:116-121)
+            self.final_classifier[-1].bias.data[0] = 0.0
+            self.final_classifier[-1].bias.data[1] = 0.0
+            self.final_classifier[-1].bias.data[2] = -0.5
+
+    def forward(self, features: torch.Tensor, bg_fg_mask: torch.Tensor):
+        if self.training:
+            raise NotImplementedError(
+                "PretrainedUNetGuidedSegmentationHead is inference only on the hiseg path (its kernels have no "
+                "backward); call .eval()")
+        return _engine().guided_head_nchw(self, features, bg_fg_mask)
+
+
 class RefinedHierarchicalSegmentationHead(nn.Module):
     """advanced/hierarchical_segmentation_refinement.py:609-804 (contour + distance aux branches)."""
 

@@ -20,7 +20,8 @@ from . import engine
 from . import export
 from . import streams
 from .effunet import EfficientNetUnet
-from .layers import RefinedHierarchicalSegmentationHead, ResidualBlock, make_act_unet, make_norm
+from .layers import (PretrainedUNetGuidedSegmentationHead, RefinedHierarchicalSegmentationHead, ResidualBlock,
+                     make_act_unet, make_norm)
 
 
 class DynamicRoIAlign(nn.Module):
@@ -133,7 +134,9 @@ class PreTrainedPeopleSegmentationUNetWrapper(nn.Module):
 
 
 class HierarchicalRGBSegmentationModelWithFullImagePretrainedUNet(nn.Module):
-    """Full-image UNet -> 2x RoIAlign -> RGB conv stack -> 258->256 combiner -> refined hierarchical head."""
+    """Full-image UNet -> 2x RoIAlign -> RGB conv stack -> head.  With any refinement flag: 258->256 combiner ->
+    refined hierarchical head; with none (the factory's default): the UNet-guided direct 3-class head, which takes
+    the features and the RoIAligned UNet logits themselves and has no combiner (rgb.py:681-727)."""
 
     def __init__(self, roi_size: Union[int, Tuple[int, int]] = 28, mask_size: Union[int, Tuple[int, int]] = 56,
                  pretrained_weights_path: str = "ext_extractor/2020-09-23a.pth", use_attention_module: bool = False,
@@ -165,19 +168,21 @@ class HierarchicalRGBSegmentationModelWithFullImagePretrainedUNet(nn.Module):
             nn.Conv2d(256, fd, 1), make_norm(norm, fd, min(g, fd)), make_act_unet(act, beta))
         use_refinement = any([use_boundary_refinement, use_progressive_upsampling, use_subpixel_conv,
                               use_contour_detection, use_distance_transform])
-        if not use_refinement:
-            raise NotImplementedError(
-                "PretrainedUNetGuidedSegmentationHead (no refinement flags) is not used by the measured configs; "
-                "hiseg builds the RefinedHierarchicalSegmentationHead path (SURVEY.md §0 item 4)")
-        self.feature_combiner = nn.Conv2d(fd + 2, fd, 1)
         ms = self.mask_size[0] if self.mask_size[0] == self.mask_size[1] else self.mask_size
-        self.segmentation_head = RefinedHierarchicalSegmentationHead(
-            in_channels=fd, mid_channels=256, num_classes=3, mask_size=ms, use_attention_module=use_attention_module,
-            use_boundary_refinement=use_boundary_refinement, use_progressive_upsampling=use_progressive_upsampling,
-            use_subpixel_conv=use_subpixel_conv, use_contour_detection=use_contour_detection,
-            use_distance_transform=use_distance_transform, normalization_type=norm, normalization_groups=g,
-            activation_function=act, activation_beta=beta, hierarchical_base_channels=base,
-            hierarchical_depth=depth)
+        if use_refinement:
+            self.feature_combiner = nn.Conv2d(fd + 2, fd, 1)
+            self.segmentation_head = RefinedHierarchicalSegmentationHead(
+                in_channels=fd, mid_channels=256, num_classes=3, mask_size=ms,
+                use_attention_module=use_attention_module, use_boundary_refinement=use_boundary_refinement,
+                use_progressive_upsampling=use_progressive_upsampling, use_subpixel_conv=use_subpixel_conv,
+                use_contour_detection=use_contour_detection, use_distance_transform=use_distance_transform,
+                normalization_type=norm, normalization_groups=g, activation_function=act, activation_beta=beta,
+                hierarchical_base_channels=base, hierarchical_depth=depth)
+        else:
+            self.segmentation_head = PretrainedUNetGuidedSegmentationHead(
+                in_channels=fd, mid_channels=256, num_classes=3, mask_size=ms,
+                use_attention_module=use_attention_module, normalization_type=norm, normalization_groups=g,
+                activation_function=act, activation_beta=beta)
         # compute precision of the HIP path: f32 (parity with the reference) or bf16 (throughput)
         self.hiseg_dtype = torch.float32
         export.record_init(self, roi_size=list(self.roi_size), mask_size=list(self.mask_size),
@@ -191,6 +196,10 @@ class HierarchicalRGBSegmentationModelWithFullImagePretrainedUNet(nn.Module):
 
     def forward(self, images: torch.Tensor, rois: torch.Tensor) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
         if self.training:  # train-mode BatchNorm / Dropout + hand-written backward (hiseg.train_engine)
+            if isinstance(self.segmentation_head, PretrainedUNetGuidedSegmentationHead):
+                raise NotImplementedError(
+                    "a model with the PretrainedUNetGuidedSegmentationHead (no refinement flag) is inference only "
+                    "on the hiseg path: the head's kernels have no backward; call model.eval()")
             from . import train_engine
             return train_engine.train_forward(self, images, rois)
         if export.tracing(images, rois):

@@ -240,7 +240,8 @@ def _channel_attention(e: Emitter, m: LY.ChannelAttentionModule, x):
 
 def emit_rgb_head(g, model: nn.Module, values: Dict[str, object], images, u, rois, scale_hw, outs: List[str]):
     """rgb.py:729-774 from the UNet logit u on; returns the tensors named in ``outs`` (export.rgb_out_templates)."""
-    from .export import _onnx_roi_align, refuse_boundary_refiner
+    from .export import _onnx_roi_align, refuse_boundary_refiner, refuse_guided_head
+    refuse_guided_head(model)        # the lowering below is the refined head's
     refuse_boundary_refiner(model)   # the batch-global min / max branch is data dependent: not lowered
     e = Emitter(g, model, values)
     (rh, rw), (mh, mw) = model.roi_size, model.mask_size

@@ -840,6 +840,96 @@ def boundary_refine_fused(em: EdgeMap, blend, w1, s1, t1, w2_frag, s2, t2, w3, b
     return out
 
 
+# ------------------------------------------------------- UNet-guided direct 3-class head (include/hiseg_guided_head.h)
+def _mask_planes(mask: torch.Tensor):
+    """The raw foreground-logit planes of a contiguous f32 [N,C,h,w] map's LAST channel: (first plane, floats
+    between two ROIs' planes)."""
+    assert mask.dtype == torch.float32 and mask.is_contiguous() and mask.dim() == 4
+    return mask[:, mask.shape[1] - 1], mask.shape[1] * mask.shape[2] * mask.shape[3]
+
+
+def guided_prep(mask: torch.Tensor, dtype: torch.dtype, out: Optional[Act] = None, want_fg_prob: bool = False,
+                want_factor: bool = False):
+    """One pass over the mask logits (f32 [N,1 or 2,h,w], the foreground channel last): p = sigmoid(m) as a
+    one-channel activation in the compute dtype (``out``: a one-channel slice of a wider buffer to write it into),
+    optionally p f32 [N,1,h,w] and the guidance factor 0.5 + 0.5 p f32 [N*h*w]."""
+    _require_gpu(mask)
+    N, _, h, w = mask.shape
+    plane, stride = _mask_planes(mask)
+    if out is None:
+        out = Act.new(N, h, w, 1, dtype, mask.device, zero=False)
+    assert out.dtype == dtype and (out.N, out.H, out.W, out.C) == (N, h, w, 1)
+    d = L.GuidedPrepDesc()
+    d.mask, d.mask_stride, d.N, d.h, d.w, d.dtype = plane, stride, N, h, w, hdtype(dtype)
+    d.fgp_c, d.fgp_cstride, d.fgp_coff = out, out.cstride, out.coff
+    fg = torch.empty(N, 1, h, w, dtype=torch.float32, device=mask.device) if want_fg_prob else None
+    factor = torch.empty(N * h * w, dtype=torch.float32, device=mask.device) if want_factor else None
+    d.fg_prob, d.factor = fg, factor
+    if N:
+        L.check(L.lib().hiseg_guided_prep_fwd(ctypes.byref(d), L.stream_ptr()), "guided_prep")
+    return out, fg, factor
+
+
+def pack_guided_attn(w1: torch.Tensor, dtype: torch.dtype, device):
+    """attention_module.0's weight [64, C, 1, 1] -> (W1 transposed f32 [C, 64], the bf16 MFMA A-operand fragments
+    [tile][kstep][lane][8] of include/hiseg_guided_head.h, or None where the matrix-core form does not apply)."""
+    hid, C = w1.shape[:2]
+    w = w1.detach().to(device=device, dtype=torch.float32).reshape(hid, C)
+    frag = None
+    if dtype == torch.bfloat16 and hid == 64 and C == 256:
+        v = w.reshape(4, 16, C // 32, 4, 8)                  # tile, row, kstep, lane group, element
+        frag = v.permute(0, 2, 3, 1, 4).contiguous().to(torch.bfloat16).reshape(-1)   # tile, kstep, (lg, row), element
+    return w.t().contiguous(), frag
+
+
+def guided_attn(x: Act, w1t: torch.Tensor, b1, w2, b2, act: int, factor: torch.Tensor, want_att: bool = False,
+                w1_frag: Optional[torch.Tensor] = None):
+    """sigmoid(w2 . act(W1 x + b1) + b2) per pixel -> (gate = att * factor f32 [P], att f32 [P] or None)."""
+    assert x.coff == 0 and x.cstride == x.C
+    P = x.N * x.H * x.W
+    assert factor.dtype == torch.float32 and factor.numel() == P and tuple(w1t.shape) == (x.C, w2.numel())
+    gate = torch.empty(P, dtype=torch.float32, device=x.t.device)
+    att = torch.empty(P, dtype=torch.float32, device=x.t.device) if want_att else None
+    d = L.GuidedAttnDesc()
+    d.dtype, d.x, d.P, d.C, d.hidden = hdtype(x.dtype), x, P, x.C, w2.numel()
+    d.w1t, d.b1, d.w2, d.b2 = w1t, b1, w2, b2
+    d.act, d.act_beta = int(act), L.act_beta(act)
+    d.factor, d.att, d.gate = factor, att, gate
+    d.w1_frag = w1_frag if x.dtype == torch.bfloat16 else None
+    if P:
+        L.check(L.lib().hiseg_guided_attn_fwd(ctypes.byref(d), L.stream_ptr()), "guided_attn")
+    return gate, att
+
+
+def guided_finish(z: Act, w3: torch.Tensor, b3: torch.Tensor, mh: int, mw: int, mask: Optional[torch.Tensor] = None,
+                  want_aux: bool = False, want_fg_prob: bool = True):
+    """final_classifier.3 (1x1 -> 3) on z, the bilinear resize to (mh, mw) and the aux tensors in one kernel.
+    Returns (logits [N,3,mh,mw], aux dict): with ``want_aux`` bg_fg_logits, target_nontarget_logits,
+    pretrained_bg_fg_mask and (``want_fg_prob``) fg_prob from the resized mask logits (f32 [N,1 or 2,h,w])."""
+    assert z.coff == 0 and z.cstride == z.C and tuple(w3.shape) == (3, z.C)
+    dev = z.t.device
+    N = z.N
+    d = L.GuidedFinishDesc()
+    d.dtype, d.z, d.N, d.h, d.w, d.C = hdtype(z.dtype), z, N, z.H, z.W, z.C
+    d.w3, d.b3, d.mh, d.mw = w3, b3, int(mh), int(mw)
+    logits = torch.empty(N, 3, mh, mw, dtype=torch.float32, device=dev)
+    d.logits = logits
+    aux = {}
+    if want_aux:
+        d.mask, d.mask_stride = _mask_planes(mask)
+        aux["bg_fg_logits"] = torch.empty(N, 2, mh, mw, dtype=torch.float32, device=dev)
+        aux["target_nontarget_logits"] = torch.empty(N, 2, mh, mw, dtype=torch.float32, device=dev)
+        aux["pretrained_bg_fg_mask"] = torch.empty(N, 1, mh, mw, dtype=torch.float32, device=dev)
+        if want_fg_prob:
+            aux["fg_prob"] = torch.empty(N, 1, mh, mw, dtype=torch.float32, device=dev)
+            d.fg_prob = aux["fg_prob"]
+        d.bg_fg_logits, d.tn_logits, d.mask_out = (aux["bg_fg_logits"], aux["target_nontarget_logits"],
+                                                   aux["pretrained_bg_fg_mask"])
+    if N:
+        L.check(L.lib().hiseg_guided_finish_fwd(ctypes.byref(d), L.stream_ptr()), "guided_finish")
+    return logits, aux
+
+
 # ------------------------------------------------------------------ distance transform (include/hiseg_distance.h)
 _DIST_TABLES = {}
 
