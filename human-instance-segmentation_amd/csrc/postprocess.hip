@@ -16,6 +16,7 @@
 //
 // No MFMA: the kernels are LDS-read / VALU work over a bandwidth-sized stream.
 #include <math.h>
+#include <hip/hip_fp16.h>
 #include "common.h"
 #include "hiseg_post.h"
 
@@ -675,4 +676,241 @@ extern "C" int hiseg_guided_filter_fwd(const float* x, const float* guide, float
   hipLaunchKernelGGL(guided_filter_kernel, dim3((unsigned)(B * Co * q.tiles)), dim3(block), lds, (hipStream_t)stream,
                      x, guide ? guide : x, out, q, radius, eps);
   return hiseg_check_launch("guided_filter");
+}
+
+// ---- DirectionalEdgeSmoothing, AdaptiveEdgeSmoothing, OptimizedEdgeSmoothing (export_edge_smoothing_onnx.py)
+//
+// The kernel shape of edge_smooth_kernel with a stencil of radius 2: one stage per iteration reads buffer a and
+// writes the 0/1 decision to buffer b, so the two-buffer budget (kResidentPx, kMaxHalo) is unchanged and the tiled
+// halo is 2 * iterations.  The optimized filter's separable Gaussian is evaluated per output pixel as the vertical
+// 5-tap sum of the five horizontal 5-tap sums it needs (25 LDS reads, the reference's two summations in their order)
+// rather than through a third LDS plane.  LDS reads: lane l reads word base + l for every tap of a row stencil and
+// base + l +- RW for the column taps, stride 1 over the 32 ds_read_b32 banks, conflict-free but for the row wrap.
+// The pre-threshold blend of the last iteration goes to `soft` from the thread that computed it.  f16 planes are
+// widened while the region is loaded and narrowed in the final store; everything between is f32.
+
+namespace hiseg {
+
+constexpr int kVarDir = 0, kVarAdaptive = 1, kVarOpt = 2;
+constexpr int kVariantRadius = 2;
+
+struct VariantParams {
+  const float* blur_strength;     // adaptive only: device arrays, element plane * stride
+  const float* edge_sensitivity;
+  const float* final_threshold;
+  long long stride;
+};
+
+__device__ __forceinline__ float load_px(const float* p) { return *p; }
+__device__ __forceinline__ float load_px(const __half* p) { return __half2float(*p); }
+__device__ __forceinline__ void store_px(float* p, float v) { *p = v; }
+__device__ __forceinline__ void store_px(__half* p, float v) { *p = __float2half(v); }
+
+// The 3x3 neighbourhood of (ly, lx) with zero padding; n[1][1] is the pixel.
+struct Nbr3 { float n[3][3]; };
+__device__ __forceinline__ Nbr3 nbr3(const Region& r, const float* a, int ly, int lx) {
+  Nbr3 q;
+#pragma unroll
+  for (int dy = 0; dy < 3; ++dy) {
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) q.n[dy][dx] = r.tap(a, ly + dy - 1, lx + dx - 1, 0.f);
+  }
+  return q;
+}
+
+__device__ __forceinline__ float laplacian8(const Nbr3& q) {
+#pragma clang fp contract(off)
+  return 8.f * q.n[1][1] - (((q.n[0][0] + q.n[0][1]) + (q.n[0][2] + q.n[1][0])) +
+                            ((q.n[1][2] + q.n[2][0]) + (q.n[2][1] + q.n[2][2])));
+}
+
+// DirectionalEdgeSmoothing.forward (:114-150) before the threshold.  IEEE f32 libm and divisions, every product
+// and sum rounded on its own in the reference's order.
+__device__ __forceinline__ float dir_blend(const Region& r, const float* a, int ly, int lx) {
+#pragma clang fp contract(off)
+  const Nbr3 q = nbr3(r, a, ly, lx);
+  const float c = q.n[1][1];
+  const float l2 = r.tap(a, ly, lx - 2, 0.f), r2 = r.tap(a, ly, lx + 2, 0.f);
+  const float u2 = r.tap(a, ly - 2, lx, 0.f), d2 = r.tap(a, ly + 2, lx, 0.f);
+  const float ex = ((((q.n[0][2] - q.n[0][0]) - 2.f * q.n[1][0]) + 2.f * q.n[1][2]) - q.n[2][0]) + q.n[2][2];
+  const float ey = ((((-q.n[0][0] - 2.f * q.n[0][1]) - q.n[0][2]) + q.n[2][0]) + 2.f * q.n[2][1]) + q.n[2][2];
+  const float mag = sqrtf((ex * ex + ey * ey) + 1e-8f);
+  const float ang = atan2f(ey, ex);
+  const float bh = (((0.1f * l2 + 0.2f * q.n[1][0]) + 0.4f * c) + 0.2f * q.n[1][2]) + 0.1f * r2;
+  const float bv = (((0.1f * u2 + 0.2f * q.n[0][1]) + 0.4f * c) + 0.2f * q.n[2][1]) + 0.1f * d2;
+  const float bd1 = (0.1f * q.n[0][0] + 0.8f * c) + 0.1f * q.n[2][2];
+  const float bd2 = (0.1f * q.n[0][2] + 0.8f * c) + 0.1f * q.n[2][0];
+  const float kQuarterPi = 0.78539816339744830962f;
+  const float ch = cosf(ang), sh = sinf(ang), c1 = cosf(ang - kQuarterPi), c2 = cosf(ang + kQuarterPi);
+  float wh = ch * ch, wv = sh * sh, wd1 = (c1 * c1) * 0.5f, wd2 = (c2 * c2) * 0.5f;
+  const float ws = (((wh + wv) + wd1) + wd2) + 1e-8f;
+  wh = wh / ws;
+  wv = wv / ws;
+  wd1 = wd1 / ws;
+  wd2 = wd2 / ws;
+  const float blurred = ((bh * wh + bv * wv) + bd1 * wd1) + bd2 * wd2;
+  return blend_f32(c, blurred, sigmoid_f32(mag * 3.0f));
+}
+
+// AdaptiveEdgeSmoothing.forward (:183-208) before the threshold; half_es = 0.5 * edge_sensitivity,
+// bf = blur_strength / 3.
+__device__ __forceinline__ float adaptive_blend(const Region& r, const float* a, int ly, int lx, float half_es,
+                                                float bf) {
+#pragma clang fp contract(off)
+  const Nbr3 q = nbr3(r, a, ly, lx);
+  const float c = q.n[1][1];
+  const float edge = fabsf(laplacian8(q)) > half_es ? 1.f : 0.f;
+  float mean = 0.f;
+#pragma unroll
+  for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+    for (int dx = -2; dx <= 2; ++dx) {
+      const float v = (dy >= -1 && dy <= 1 && dx >= -1 && dx <= 1) ? q.n[dy + 1][dx + 1] : r.tap(a, ly + dy, lx + dx, 0.f);
+      mean = mean + 0.04f * v;
+    }
+  }
+  const float smoothed = blend_f32(c, mean, bf);
+  return blend_f32(c, smoothed, edge);
+}
+
+// OptimizedEdgeSmoothing.forward (:293-310) before the threshold.
+__device__ __forceinline__ float opt_blend(const Region& r, const float* a, int ly, int lx) {
+#pragma clang fp contract(off)
+  const float w[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+  float rows[5][5];
+#pragma unroll
+  for (int dy = 0; dy < 5; ++dy) {
+#pragma unroll
+    for (int dx = 0; dx < 5; ++dx) rows[dy][dx] = r.tap(a, ly + dy - 2, lx + dx - 2, 0.f);
+  }
+  Nbr3 q;
+#pragma unroll
+  for (int dy = 0; dy < 3; ++dy) {
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) q.n[dy][dx] = rows[dy + 1][dx + 1];
+  }
+  float blurred = 0.f;
+#pragma unroll
+  for (int dy = 0; dy < 5; ++dy) {
+    float h = 0.f;
+#pragma unroll
+    for (int dx = 0; dx < 5; ++dx) h = h + w[dx] * rows[dy][dx];
+    blurred = blurred + w[dy] * h;
+  }
+  const float scaled = fabsf(laplacian8(q)) * 3.0f;
+  const float e = fminf(fmaxf((scaled + 0.5f) * 0.5f, 0.f), 1.f);
+  return blend_f32(q.n[1][1], blurred, e);
+}
+
+// TI / TO: the types of the planes x and out.  f32 in with f16 out rounds x to f16 while it is loaded: the f16 path
+// on an f32 mask (OptimizedEdgeSmoothing(use_fp16=True) behind the wrapper's f32 masks) without a cast pass.
+template <int KIND, typename TI, typename TO>
+__global__ void __launch_bounds__(1024) edge_variant_kernel(const TI* __restrict__ x, TO* __restrict__ out,
+                                                            float* __restrict__ soft, PostGeom g, VariantParams vp,
+                                                            int iterations) {
+  extern __shared__ float post_lds[];
+  const long long plane = blockIdx.x / g.tiles;
+  const Region r = region_of(g, (int)(blockIdx.x % g.tiles));
+  const long long HW = (long long)g.H * g.W;
+  const int n = r.size();
+  float* a = post_lds;
+  float* b = post_lds + n;
+
+  float thr = 0.5f, half_es = 0.f, bf = 0.f;
+  if constexpr (KIND == kVarAdaptive) {
+    const long long pi = plane * vp.stride;
+    thr = vp.final_threshold[pi];
+    half_es = 0.5f * vp.edge_sensitivity[pi];
+    bf = vp.blur_strength[pi] / 3.0f;
+  }
+
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const int ly = i / r.RW, lx = i - ly * r.RW;
+    float v = 0.f;
+    if (r.in_image(ly, lx)) {
+      v = load_px(x + plane * HW + (long long)(r.y0 + ly) * g.W + (r.x0 + lx));
+      if constexpr (sizeof(TI) > sizeof(TO)) v = __half2float(__float2half(v));
+    }
+    a[i] = v;
+  }
+  __syncthreads();
+
+  for (int it = 0; it < iterations; ++it) {
+    const bool want_soft = soft != nullptr && it == iterations - 1;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+      const int ly = i / r.RW, lx = i - ly * r.RW;
+      float o = 0.f;
+      if (r.in_image(ly, lx)) {
+        float v;
+        if constexpr (KIND == kVarDir) v = dir_blend(r, a, ly, lx);
+        else if constexpr (KIND == kVarAdaptive) v = adaptive_blend(r, a, ly, lx, half_es, bf);
+        else v = opt_blend(r, a, ly, lx);
+        o = v > thr ? 1.f : 0.f;
+        if (want_soft && ly >= g.R && ly < g.R + g.TH && lx >= g.R && lx < g.R + g.TW)
+          soft[plane * HW + (long long)(r.y0 + ly) * g.W + (r.x0 + lx)] = v;
+      }
+      b[i] = o;
+    }
+    __syncthreads();
+    float* t = a; a = b; b = t;
+  }
+  TO* dst = out + plane * HW;
+  for (int i = threadIdx.x; i < g.TH * g.TW; i += blockDim.x) {
+    const int ty = i / g.TW, tx = i - ty * g.TW;
+    const int gy = r.y0 + g.R + ty, gx = r.x0 + g.R + tx;
+    if (gy < g.H && gx < g.W) store_px(dst + (long long)gy * g.W + gx, a[(ty + g.R) * r.RW + tx + g.R]);
+  }
+}
+
+}  // namespace hiseg
+
+namespace {
+
+template <int KIND, typename TI, typename TO>
+int edge_variant(const char* what, const TI* x, TO* out, float* soft, long long NC, int H, int W,
+                 const VariantParams& vp, int iterations, int force_tiled, hiseg_stream_t stream) {
+  HISEG_REQUIRE(iterations >= 1, HISEG_ERR_BAD_ARG, "%s: iterations %d", what, iterations);
+  PostPlan p;
+  const long long halo = (long long)iterations * kVariantRadius;
+  const int st = post_plan(what, x, out, NC, H, W, halo > kMaxHalo ? kMaxHalo + 1 : (int)halo, force_tiled, &p);
+  if (st != HISEG_OK || p.grid == 0) return st;
+  HISEG_REQUIRE((const void*)x != (const void*)out && (const void*)soft != (const void*)x &&
+                    (const void*)soft != (const void*)out,
+                HISEG_ERR_BAD_ARG, "%s: x, out and soft alias", what);
+  if constexpr (KIND == kVarAdaptive) {
+    HISEG_REQUIRE(vp.blur_strength && vp.edge_sensitivity && vp.final_threshold && vp.stride >= 0, HISEG_ERR_BAD_ARG,
+                  "%s: null parameter array or negative param_stride %lld", what, vp.stride);
+  }
+  post_launch(edge_variant_kernel<KIND, TI, TO>, p, (hipStream_t)stream, x, out, soft, p.g, vp, iterations);
+  return hiseg_check_launch(what);
+}
+
+}  // namespace
+
+extern "C" int hiseg_dir_edge_smooth_fwd(const float* x, float* out, float* soft, long long NC, int H, int W,
+                                         int iterations, int force_tiled, hiseg_stream_t stream) {
+  return edge_variant<kVarDir, float, float>("dir_edge_smooth", x, out, soft, NC, H, W, VariantParams{}, iterations,
+                                      force_tiled, stream);
+}
+
+extern "C" int hiseg_adaptive_edge_smooth_fwd(const float* x, float* out, float* soft, long long NC, int H, int W,
+                                              const float* blur_strength, const float* edge_sensitivity,
+                                              const float* final_threshold, long long param_stride, int iterations,
+                                              int force_tiled, hiseg_stream_t stream) {
+  const VariantParams vp{blur_strength, edge_sensitivity, final_threshold, param_stride};
+  return edge_variant<kVarAdaptive, float, float>("adaptive_edge_smooth", x, out, soft, NC, H, W, vp, iterations,
+                                           force_tiled, stream);
+}
+
+extern "C" int hiseg_opt_edge_smooth_fwd(int dtype, const void* x, void* out, float* soft, long long NC, int H, int W,
+                                         int iterations, int force_tiled, hiseg_stream_t stream) {
+  if (dtype == HISEG_POST_F16)
+    return edge_variant<kVarOpt, __half, __half>("opt_edge_smooth", (const __half*)x, (__half*)out, soft, NC, H, W,
+                                                 VariantParams{}, iterations, force_tiled, stream);
+  if (dtype == HISEG_POST_F32_TO_F16)
+    return edge_variant<kVarOpt, float, __half>("opt_edge_smooth", (const float*)x, (__half*)out, soft, NC, H, W,
+                                                VariantParams{}, iterations, force_tiled, stream);
+  HISEG_REQUIRE(dtype == HISEG_POST_F32, HISEG_ERR_BAD_DTYPE, "opt_edge_smooth: dtype %d (f32 or f16 planes)", dtype);
+  return edge_variant<kVarOpt, float, float>("opt_edge_smooth", (const float*)x, (float*)out, soft, NC, H, W,
+                                      VariantParams{}, iterations, force_tiled, stream);
 }

@@ -30,8 +30,9 @@ from .distill import (  # noqa: F401,E402
 from .kd import (  # noqa: F401,E402
     DistillationLoss, DistillationModelWrapper, create_distilled_rgb_hierarchical_model)
 from .postprocess import (  # noqa: F401,E402
-    BilateralFilter, BinaryMaskBilateralFilter, BinaryMaskEdgeSmoothing, EdgePreservingFilter, FastBilateralFilter,
-    MorphologicalBilateralFilter, MultiClassEdgeSmoothing, apply_edge_smoothing_to_masks)
+    AdaptiveEdgeSmoothing, BilateralFilter, BinaryMaskBilateralFilter, BinaryMaskEdgeSmoothing,
+    DirectionalEdgeSmoothing, EdgePreservingFilter, FastBilateralFilter, MorphologicalBilateralFilter,
+    MultiClassEdgeSmoothing, OptimizedEdgeSmoothing, apply_edge_smoothing_to_masks)
 from .compose import InstanceMapComposer, instance_colors  # noqa: F401,E402
 
 __version__ = "0.2.0"

@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("HISEG_LIB", os.path.join(_HERE, "libhiseg.so"))
 
 HISEG_F32 = 0
 HISEG_BF16 = 1
+HISEG_POST_F32, HISEG_POST_F16, HISEG_POST_F32_TO_F16 = 0, 2, 3   # include/hiseg_post.h hiseg_post_dtype
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SILU, ACT_GELU, ACT_SWISH = 0, 1, 2, 3, 4, 5
 
 
@@ -404,6 +405,9 @@ def _declare(lib):
         "hiseg_morph_bilateral_fwd": ([P, P, c_ll, c_int, c_int, c_int, c_float, c_int, c_int, P], c_int),
         "hiseg_bilateral_fwd": ([P, P, c_ll, c_int, c_int, c_int, c_float, c_float, P], c_int),
         "hiseg_guided_filter_fwd": ([P, P, P, c_ll, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P], c_int),
+        "hiseg_dir_edge_smooth_fwd": ([P, P, P, c_ll, c_int, c_int, c_int, c_int, P], c_int),
+        "hiseg_adaptive_edge_smooth_fwd": ([P, P, P, c_ll, c_int, c_int, P, P, P, c_ll, c_int, c_int, P], c_int),
+        "hiseg_opt_edge_smooth_fwd": ([c_int, P, P, P, c_ll, c_int, c_int, c_int, c_int, P], c_int),
         # ---- boundary refinement stage and active-contour loss (include/hiseg_refine.h)
         "hiseg_edge_map_ws": ([c_int, c_int, c_int], c_ll),
         "hiseg_edge_map_fwd": ([P, c_int, c_int, c_int, P, P, P, P, c_int, c_int, P, P], c_int),

@@ -766,6 +766,100 @@ def guided_filter(x: torch.Tensor, guide: Optional[torch.Tensor] = None, radius:
     return out
 
 
+# The directional, adaptive and optimized edge-smoothing filters: stencils of radius 2.  `return_soft` adds the f32
+# blend of the last iteration before its threshold.
+
+
+def _variant_planes(x: torch.Tensor, what: str, dtypes=(torch.float32,)):
+    _require_gpu(x)
+    if x.dim() < 2:
+        raise ValueError(f"{what}: expected [..., H, W] planes, got shape {tuple(x.shape)}")
+    if x.dtype not in dtypes:
+        raise ValueError(f"{what}: expected planes of {' or '.join(str(d) for d in dtypes)}, got {x.dtype}")
+    x = x.contiguous()
+    H, W = x.shape[-2:]
+    return x, (x.numel() // (H * W) if H * W else 0), H, W
+
+
+def _variant_run(x, H, W, iterations, return_soft, force_tiled, launch, out_dtype=None):
+    """`launch(x, out, soft_ptr, n)` once per chunk of iterations; the soft blend comes from the last chunk."""
+    chunks = _post_chunks(iterations, H, W, 2, force_tiled)
+    soft = None
+    for i, n in enumerate(chunks):
+        out = torch.empty_like(x, dtype=out_dtype)
+        if return_soft and i == len(chunks) - 1:
+            soft = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        launch(x, out, _ptr(soft), n)
+        x = out
+    return (x, soft) if return_soft else x
+
+
+def dir_edge_smooth(x: torch.Tensor, iterations: int = 1, *, return_soft: bool = False, _force_tiled: bool = False):
+    """DirectionalEdgeSmoothing applied `iterations` times to every H x W plane of x; f32 in, f32 0/1 out."""
+    x, NC, H, W = _variant_planes(x, "dir_edge_smooth")
+
+    def launch(src, out, soft, n):
+        L.check(L.lib().hiseg_dir_edge_smooth_fwd(src.data_ptr(), out.data_ptr(), soft, NC, H, W, n,
+                                                  int(_force_tiled), L.stream_ptr()), "dir_edge_smooth")
+    return _variant_run(x, H, W, iterations, return_soft, _force_tiled, launch)
+
+
+def adaptive_edge_smooth(x: torch.Tensor, blur_strength: torch.Tensor, edge_sensitivity: torch.Tensor,
+                         final_threshold: torch.Tensor, iterations: int = 1, *, return_soft: bool = False,
+                         _force_tiled: bool = False):
+    """AdaptiveEdgeSmoothing applied `iterations` times.  The parameters are f32 tensors on x's device with one
+    element (every plane), one per plane, or -- for a [B,C,H,W] x -- one per image as the reference's [B,1]; they
+    are read by the kernel only."""
+    x, NC, H, W = _variant_planes(x, "adaptive_edge_smooth")
+    params = []
+    for name, p in (("blur_strength", blur_strength), ("edge_sensitivity", edge_sensitivity),
+                    ("final_threshold", final_threshold)):
+        if not isinstance(p, torch.Tensor) or p.dtype != torch.float32:
+            raise ValueError(f"adaptive_edge_smooth: {name} must be a float32 tensor, got "
+                             f"{p.dtype if isinstance(p, torch.Tensor) else type(p).__name__}")
+        _require_gpu(p)
+        if p.device != x.device:
+            raise ValueError(f"adaptive_edge_smooth: {name} is on {p.device}, the planes on {x.device}")
+        params.append(p)
+    if all(p.numel() == 1 for p in params):
+        stride = 0
+        params = [p.contiguous() for p in params]
+    else:
+        stride = 1
+        for i, p in enumerate(params):
+            if p.numel() == 1:
+                p = p.reshape(1).expand(NC)
+            elif x.dim() == 4 and p.numel() == x.shape[0] and p.numel() != NC:
+                p = p.reshape(-1, 1).expand(-1, x.shape[1])
+            elif p.numel() != NC:
+                raise ValueError(f"adaptive_edge_smooth: a parameter of {p.numel()} elements for {NC} planes "
+                                 f"(shape {tuple(x.shape)})")
+            params[i] = p.contiguous()
+    bs, es, ft = params
+
+    def launch(src, out, soft, n):
+        L.check(L.lib().hiseg_adaptive_edge_smooth_fwd(src.data_ptr(), out.data_ptr(), soft, NC, H, W, bs.data_ptr(),
+                                                       es.data_ptr(), ft.data_ptr(), stride, n, int(_force_tiled),
+                                                       L.stream_ptr()), "adaptive_edge_smooth")
+    return _variant_run(x, H, W, iterations, return_soft, _force_tiled, launch)
+
+
+def opt_edge_smooth(x: torch.Tensor, iterations: int = 1, *, to_fp16: bool = False, return_soft: bool = False,
+                    _force_tiled: bool = False):
+    """OptimizedEdgeSmoothing applied `iterations` times: f32 planes in and out, or f16 planes in and out (f32
+    arithmetic on the f16 values).  `to_fp16` on f32 planes: the kernel rounds them to f16 while it reads them and
+    writes f16 planes -- the bits of opt_edge_smooth(x.half()) without the cast pass."""
+    x, NC, H, W = _variant_planes(x, "opt_edge_smooth", (torch.float32, torch.float16))
+
+    def launch(src, out, soft, n):
+        dtype = (L.HISEG_POST_F16 if src.dtype == torch.float16 else
+                 L.HISEG_POST_F32_TO_F16 if out.dtype == torch.float16 else L.HISEG_POST_F32)
+        L.check(L.lib().hiseg_opt_edge_smooth_fwd(dtype, src.data_ptr(), out.data_ptr(), soft, NC, H, W, n,
+                                                  int(_force_tiled), L.stream_ptr()), "opt_edge_smooth")
+    return _variant_run(x, H, W, iterations, return_soft, _force_tiled, launch,
+                        out_dtype=torch.float16 if to_fp16 else None)
+
+
 # ---- boundary refinement stage (include/hiseg_refine.h): f32 NCHW logits [N,3,H,W]
 
 

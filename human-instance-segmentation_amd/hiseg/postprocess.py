@@ -27,7 +27,8 @@ import torch.nn as nn
 from . import ops
 
 __all__ = ["BinaryMaskEdgeSmoothing", "MultiClassEdgeSmoothing", "apply_edge_smoothing_to_masks", "BilateralFilter",
-           "FastBilateralFilter", "EdgePreservingFilter", "BinaryMaskBilateralFilter", "MorphologicalBilateralFilter"]
+           "FastBilateralFilter", "EdgePreservingFilter", "BinaryMaskBilateralFilter", "MorphologicalBilateralFilter",
+           "DirectionalEdgeSmoothing", "AdaptiveEdgeSmoothing", "OptimizedEdgeSmoothing"]
 
 
 def _check_kernel_size(kernel_size: int, what: str = "Kernel size", lo: int = 3) -> None:
@@ -233,3 +234,128 @@ class MorphologicalBilateralFilter(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         _nchw(x, "MorphologicalBilateralFilter")
         return ops.morph_bilateral(x, self.kernel_size, self.sigma, self.morph_size)
+
+
+# ---- the directional, adaptive and optimized graphs of export_edge_smoothing_onnx.py
+#
+# The registered buffers (and the three frozen convolutions of OptimizedEdgeSmoothing) carry the reference's
+# state_dict keys and values so that its checkpoints load strictly.  The kernels use those taps as constants: a
+# loaded value that differs from the reference's raises, instead of being ignored.
+
+
+def _kernel4(rows) -> torch.Tensor:
+    return torch.tensor(rows, dtype=torch.float32).unsqueeze(0).unsqueeze(0)
+
+
+_LAPLACIAN = [[-1, -1, -1], [-1, 8, -1], [-1, -1, -1]]
+_GAUSS5 = [0.0625, 0.25, 0.375, 0.25, 0.0625]
+
+
+class _FixedTaps(nn.Module):
+    """A module whose state is constant: remembers it at construction and checks every load against it."""
+
+    def _freeze_taps(self) -> None:
+        self._taps = {k: v.detach().clone() for k, v in self.state_dict().items()}
+        self.register_load_state_dict_post_hook(_FixedTaps._check_taps)
+
+    @staticmethod
+    def _check_taps(module, incompatible_keys) -> None:
+        for k, v in module.state_dict().items():
+            want = module._taps[k]
+            if v.shape != want.shape or not torch.equal(v.detach().float().cpu(), want):
+                raise ValueError(f"{type(module).__name__}: loaded '{k}' differs from the reference's constant; the "
+                                 "kernel computes with the fixed taps")
+
+    @staticmethod
+    def _mask(mask: torch.Tensor, what: str, dtypes=(torch.float32,)) -> torch.Tensor:
+        if not isinstance(mask, torch.Tensor) or mask.dim() != 4:
+            raise ValueError(f"{what}: expected a (B, C, H, W) mask, got "
+                             f"{tuple(mask.shape) if isinstance(mask, torch.Tensor) else type(mask).__name__}")
+        if mask.dtype not in dtypes:
+            raise ValueError(f"{what}: expected a mask of {' or '.join(str(d) for d in dtypes)}, got {mask.dtype}")
+        return mask
+
+
+class DirectionalEdgeSmoothing(_FixedTaps):
+    """Direction-aware edge smoothing (export_edge_smoothing_onnx.py:63-155): (B, C, H, W) float32 in, 0/1 float32
+    out.  ``num_directions`` is stored and never read, as in the reference."""
+
+    def __init__(self, num_directions: int = 4):
+        super().__init__()
+        self.num_directions = num_directions
+        self.register_buffer("sobel_x", _kernel4([[-1, 0, 1], [-2, 0, 2], [-1, 0, 1]]))
+        self.register_buffer("sobel_y", _kernel4([[-1, -2, -1], [0, 0, 0], [1, 2, 1]]))
+        self.register_buffer("h_blur", _kernel4([[0.1, 0.2, 0.4, 0.2, 0.1]]))
+        self.register_buffer("v_blur", _kernel4([[0.1], [0.2], [0.4], [0.2], [0.1]]))
+        self.register_buffer("diag1_blur", _kernel4([[0.1, 0.0, 0.0], [0.0, 0.8, 0.0], [0.0, 0.0, 0.1]]))
+        self.register_buffer("diag2_blur", _kernel4([[0.0, 0.0, 0.1], [0.0, 0.8, 0.0], [0.1, 0.0, 0.0]]))
+        self._freeze_taps()
+
+    def forward(self, mask: torch.Tensor, iterations: int = 1, return_soft: bool = False):
+        self._mask(mask, "DirectionalEdgeSmoothing")
+        return ops.dir_edge_smooth(mask, iterations, return_soft=return_soft)
+
+
+class AdaptiveEdgeSmoothing(_FixedTaps):
+    """Edge smoothing with run-time parameters (export_edge_smoothing_onnx.py:158-213): ``forward(mask,
+    blur_strength, edge_sensitivity, final_threshold)`` with (B, 1) float32 tensors on the mask's device (one value
+    per image; one element broadcasts).  The kernel reads them on the device: no host synchronisation, and a
+    captured graph sees the values they hold at replay.
+
+    The three parameters may also be given at construction, as floats or tensors; they are then kept on the
+    module's device and ``forward(mask)`` is a callable of one tensor (a serving hook)."""
+
+    def __init__(self, blur_strength=None, edge_sensitivity=None, final_threshold=None):
+        super().__init__()
+        self.register_buffer("laplacian_kernel", _kernel4(_LAPLACIAN))
+        self._freeze_taps()
+        for name, v in (("blur_strength", blur_strength), ("edge_sensitivity", edge_sensitivity),
+                        ("final_threshold", final_threshold)):
+            if v is not None and not isinstance(v, torch.Tensor):
+                v = torch.tensor([float(v)], dtype=torch.float32)
+            if v is not None and v.dtype != torch.float32:
+                raise ValueError(f"AdaptiveEdgeSmoothing: {name} must be a float or a float32 tensor, got {v.dtype}")
+            self.register_buffer("default_" + name, v, persistent=False)
+
+    def forward(self, mask: torch.Tensor, blur_strength: Optional[torch.Tensor] = None,
+                edge_sensitivity: Optional[torch.Tensor] = None, final_threshold: Optional[torch.Tensor] = None,
+                iterations: int = 1, return_soft: bool = False):
+        self._mask(mask, "AdaptiveEdgeSmoothing")
+        params = []
+        for name, v in (("blur_strength", blur_strength), ("edge_sensitivity", edge_sensitivity),
+                        ("final_threshold", final_threshold)):
+            v = getattr(self, "default_" + name) if v is None else v
+            if v is None:
+                raise ValueError(f"AdaptiveEdgeSmoothing: {name} was given neither to forward nor at construction")
+            params.append(v)
+        return ops.adaptive_edge_smooth(mask, *params, iterations, return_soft=return_soft)
+
+
+class OptimizedEdgeSmoothing(_FixedTaps):
+    """The deployment variant (export_edge_smoothing_onnx.py:216-318): Laplacian, separable 5-tap Gaussian and a
+    clamped linear ramp in place of the sigmoid.  ``use_fp16=True``: a float32 mask is rounded to float16 as the
+    reference does -- by the kernel while it reads the mask, not by a cast pass -- a float16 mask is taken as it
+    is, and the 0/1 result is float16 (float32 arithmetic on the float16 values).
+    ``use_fp16=False``: float32 in and out.  The three convolutions exist for the reference's state_dict keys and
+    are never called."""
+
+    def __init__(self, use_fp16: bool = True):
+        super().__init__()
+        self.use_fp16 = use_fp16
+        self.edge_detector = nn.Conv2d(1, 1, kernel_size=3, padding=1, groups=1, bias=False)
+        self.gaussian_h = nn.Conv2d(1, 1, kernel_size=(1, 5), padding=(0, 2), bias=False)
+        self.gaussian_v = nn.Conv2d(1, 1, kernel_size=(5, 1), padding=(2, 0), bias=False)
+        for conv, taps, shape in ((self.edge_detector, _LAPLACIAN, (1, 1, 3, 3)), (self.gaussian_h, _GAUSS5, (1, 1, 1, 5)),
+                                  (self.gaussian_v, _GAUSS5, (1, 1, 5, 1))):
+            conv.weight.data = torch.tensor(taps, dtype=torch.float32).reshape(shape)
+            conv.weight.requires_grad = False
+        self.register_buffer("edge_scale", torch.tensor(3.0))
+        self.register_buffer("threshold", torch.tensor(0.5))
+        self._freeze_taps()
+
+    def forward(self, mask: torch.Tensor, iterations: int = 1, return_soft: bool = False):
+        if self.use_fp16:
+            self._mask(mask, "OptimizedEdgeSmoothing", (torch.float32, torch.float16))
+        else:
+            self._mask(mask, "OptimizedEdgeSmoothing(use_fp16=False)")
+        return ops.opt_edge_smooth(mask, iterations, to_fp16=self.use_fp16, return_soft=return_soft)

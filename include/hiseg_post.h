@@ -4,7 +4,8 @@
  * graphs by export_edge_smoothing_onnx.py and export_bilateral_filter.py).  Conventions as in hiseg.h.
  *
  * Every entry point takes f32 NCHW planes with C folded into N: NC contiguous planes of H x W, x and out distinct
- * buffers of the same size.  All arithmetic is f32.  NC * H * W == 0 returns HISEG_OK without a launch.
+ * buffers of the same size (hiseg_opt_edge_smooth_fwd alone also takes f16 planes).  All arithmetic is f32.
+ * NC * H * W == 0 returns HISEG_OK without a launch.
  *
  * Kernel forms (csrc/postprocess.hip).  A plane of at most 20480 pixels (two f32 working copies in the 160 KB of
  * LDS: the 64x48 and 128x96 instance masks) is owned by one workgroup: every iteration and stage runs LDS to LDS,
@@ -85,6 +86,40 @@ int hiseg_bilateral_fwd(const float* x, float* out, long long NC, int H, int W, 
  * same bits. */
 int hiseg_guided_filter_fwd(const float* x, const float* guide, float* out, long long B, int Cx, int Cg, int H, int W,
                             int radius, float eps, int force_tiled, hiseg_stream_t stream);
+
+/* ---- The other three edge-smoothing graphs of export_edge_smoothing_onnx.py.  All three are stencils of radius 2
+ * (hiseg_post_max_iterations(H, W, 2, force_tiled): 16 iterations per launch in the tiled form), applied
+ * `iterations` >= 1 times, every convolution zero padded, the blend m*(1-e) + b*e evaluated as in
+ * hiseg_edge_smooth_fwd (each operation rounded to f32 on its own, no fused multiply-add).  x, out and soft are
+ * distinct buffers of NC planes.  soft, when not NULL, receives the f32 blend of the LAST iteration before its
+ * threshold (out is the decision soft > threshold); each element of out and of soft is written by one thread.
+ * Both kernel forms give the same bits, and N iterations in one launch the same bits as N launches. */
+
+/* DirectionalEdgeSmoothing.forward (:114-155): Sobel ex, ey; mag = sqrt(ex^2 + ey^2 + 1e-8), t = atan2(ey, ex); the
+ * blurs 1x5 and 5x1 (0.1, 0.2, 0.4, 0.2, 0.1) and the two 3x3 diagonals (0.1, 0.8, 0.1); weights cos^2 t, sin^2 t,
+ * 0.5 cos^2(t - pi/4), 0.5 cos^2(t + pi/4), each divided by (their sum + 1e-8); e = sigmoid(3 mag); > 0.5.  The
+ * f32 libm functions and the divisions are the IEEE ones, not the fast intrinsics. */
+int hiseg_dir_edge_smooth_fwd(const float* x, float* out, float* soft, long long NC, int H, int W, int iterations,
+                              int force_tiled, hiseg_stream_t stream);
+
+/* AdaptiveEdgeSmoothing.forward (:172-213): e = (|3x3 Laplacian| > 0.5 edge_sensitivity) as 0 / 1, a = 5x5 mean,
+ * s = m*(1 - bs/3) + a*(bs/3), m*(1-e) + s*e, > final_threshold.  The three parameters are DEVICE arrays read by the
+ * kernel, never by the host: plane p uses element p * param_stride of each, so param_stride 0 broadcasts element 0
+ * to every plane and 1 gives every plane its own (NC elements). */
+int hiseg_adaptive_edge_smooth_fwd(const float* x, float* out, float* soft, long long NC, int H, int W,
+                                   const float* blur_strength, const float* edge_sensitivity,
+                                   const float* final_threshold, long long param_stride, int iterations,
+                                   int force_tiled, hiseg_stream_t stream);
+
+/* OptimizedEdgeSmoothing.forward (:279-318): 3x3 Laplacian, the separable (1, 4, 6, 4, 1)/16 Gaussian (horizontal
+ * sums first, then the vertical sum of those), e = clamp((3 |lap| + 0.5) * 0.5, 0, 1), the blend, > 0.5.  dtype is
+ * the type of the planes x and out: HISEG_POST_F32 (use_fp16=False), HISEG_POST_F16 (use_fp16=True), or
+ * HISEG_POST_F32_TO_F16 (use_fp16=True on an f32 mask: x is f32 and rounded to f16, to nearest even, while it is
+ * read; out is f16; the same bits as casting x first), else HISEG_ERR_BAD_DTYPE.  With f16 planes the arithmetic is
+ * f32 on the f16 values read, and the 0 / 1 written is exact in f16; soft is f32 either way. */
+enum hiseg_post_dtype { HISEG_POST_F32 = 0, HISEG_POST_F16 = 2, HISEG_POST_F32_TO_F16 = 3 };
+int hiseg_opt_edge_smooth_fwd(int dtype, const void* x, void* out, float* soft, long long NC, int H, int W,
+                              int iterations, int force_tiled, hiseg_stream_t stream);
 
 #ifdef __cplusplus
 }
