@@ -20,13 +20,17 @@ from .distance_loss import (  # noqa: F401,E402
     AdaptiveBoundaryLoss, DistanceAwareSegmentationLoss, create_distance_aware_loss)
 from .optim import FusedAdamW, cosine_lr  # noqa: F401,E402
 from .graphs import GraphedStep, GraphedBranchStep  # noqa: F401,E402
-from .checkpoint import load_teacher_checkpoint, resume_from_checkpoint, save_checkpoint  # noqa: F401,E402
+from .checkpoint import (  # noqa: F401,E402
+    load_teacher_checkpoint, resume_distillation_checkpoint, resume_from_checkpoint, save_checkpoint,
+    save_distillation_checkpoint)
 from .data import GpuRoiBatchBuilder, resize_bilinear_pil  # noqa: F401,E402
 from .metrics import (  # noqa: F401,E402
     SegmentationMetrics, calculate_confusion_matrix, calculate_detection_metrics, calculate_iou, evaluate_model,
 )
 from .distill import (  # noqa: F401,E402
     DistillationUNetWrapper, UNetDecoderOnly, UNetDistillationLoss, create_unet_distillation_model)
+from .distill_eval import (  # noqa: F401,E402
+    binary_seg_stats, distill_metrics_from_counts, evaluate_distillation, update_adaptive_distillation)
 from .kd import (  # noqa: F401,E402
     DistillationLoss, DistillationModelWrapper, create_distilled_rgb_hierarchical_model)
 from .postprocess import (  # noqa: F401,E402

@@ -392,6 +392,7 @@ def _declare(lib):
         "hiseg_distill_loss_fwd": ([ctypes.POINTER(DistillCfg), c_int, c_int, c_int, P, P, P, P, P, P], c_int),
         "hiseg_distill_loss_bwd": ([ctypes.POINTER(DistillCfg), c_int, c_int, c_int, P, P, P, P, P, P, P], c_int),
         "hiseg_seg_confusion": ([P, c_int, P, P, c_int, c_int, c_ll, P, P], c_int),
+        "hiseg_binary_seg_stats": ([P, c_int, P, c_int, P, c_int, c_int, c_ll, P, P], c_int),
         "hiseg_pil_bilinear_table": ([c_int, c_int, P, P, P], c_int),
         "hiseg_pil_resample_h": ([P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P], c_int),
         "hiseg_pil_resample_v": ([P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P], c_int),

@@ -35,10 +35,13 @@ class _LazyDict(Mapping):
     def __init__(self, out: torch.Tensor, keys):
         self._out, self._keys, self._vals = out, keys, None
 
+    def _materialise(self, host):
+        # host: the DISTILL_NOUT values of _out (hiseg.distill_eval brings many dicts over in one copy)
+        self._vals = {k: float(host[i]) for i, k in enumerate(_DICT_KEYS) if k in self._keys}
+
     def _get(self):
         if self._vals is None:
-            host = self._out.detach().cpu().tolist()
-            self._vals = {k: float(host[i]) for i, k in enumerate(_DICT_KEYS) if k in self._keys}
+            self._materialise(self._out.detach().cpu().tolist())
         return self._vals
 
     def __getitem__(self, k):

@@ -34,6 +34,43 @@ extern "C" {
 int hiseg_seg_confusion(const void* logits, int dtype, const long long* pred_labels, const long long* target,
                         int N, int C, long long HW, unsigned long long* conf, hiseg_stream_t stream);
 
+/*
+ * Distillation validation (train_distillation_staged.py:369-581, evaluate): student mIoU, teacher mIoU and
+ * teacher-student agreement of the binary UNet pair.  The reference builds them from about 40 elementwise and
+ * reduction passes over [B,1,H,W] per batch; every one of those numbers is a function of eight counts per
+ * sample, the joint histogram of the three bits (mask, teacher, student):
+ *
+ *   counts[b][4*m + 2*t + s] += #{ pixels of sample b with mask bit m, teacher bit t, student bit s }
+ *
+ * Foreground predicate of a logit x (the reference's `sigmoid(x) > 0.5`, :444-446):
+ *
+ *   bit(x) = x > 0x1.8p-24f        (1.5 * 2^-24, about 8.94e-8; compared in f32)
+ *
+ * which is `1.0f / (1.0f + expf(-x)) > 0.5f` with every f32 operation correctly rounded: the quotient exceeds
+ * 0.5 iff fl(1 + fl(exp(-x))) < 2, 1 + (1 - 2^-24) ties to the even 2.0, so fl(exp(-x)) <= 1 - 2^-23 is
+ * needed, i.e. exp(-x) below the midpoint 1 - 1.5 * 2^-24, i.e. x > 1.5 * 2^-24 (x = 1.5 * 2^-24 itself gives
+ * exp(-x) just above that midpoint).  So 0.0, -0.0, every negative value, NaN and 2^-24 are background; 2^-23,
+ * every x >= 1e-6 and +inf are foreground.  Inside the open band (0, 1e-6) a sigmoid whose exp is not
+ * correctly rounded may answer differently (torch's CPU and GPU kernels are such implementations): no parity
+ * is claimed there.  bf16 logits are widened to f32 and then compared; torch's bf16 sigmoid rounds its result
+ * to bf16 first, where 0.5 + 2^-9 is the first value above 0.5, so torch on bf16 logits calls small positive
+ * logits background that this predicate (and the reference's f32 path) calls foreground.
+ *
+ * A mask pixel is foreground iff mask > 0.5 (:449; NaN is background; any non-zero uint8 is foreground).
+ */
+enum { HISEG_U8 = 2 };   /* mask dtype of hiseg_binary_seg_stats (beside HISEG_F32) */
+
+/* Accumulates into counts (uint64, [B][8], zeroed by the caller for a fresh count).
+ *   student  [B][HW] logits, s_dtype HISEG_F32 or HISEG_BF16
+ *   teacher  [B][HW] logits, t_dtype HISEG_F32 or HISEG_BF16; null: t = s (the reference's teacher-less
+ *            mode, :445-448), t_dtype ignored
+ *   mask     [B][HW], m_dtype HISEG_F32 or HISEG_U8
+ * B <= 65535.  One pass, 12 bytes per pixel for f32 inputs; integer counts, so the result is exact and
+ * independent of the launch shape; no host synchronisation. */
+int hiseg_binary_seg_stats(const void* student, int s_dtype, const void* teacher, int t_dtype,
+                           const void* mask, int m_dtype, int B, long long HW, unsigned long long* counts,
+                           hiseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
