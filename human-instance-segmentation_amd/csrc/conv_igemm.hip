@@ -18,6 +18,7 @@
 // groups of the fragment reads (MI355X_MICROARCH.md §LDS) and for the row-wise stores.
 // Two LDS stages; the next K block is gathered into registers while the current one feeds
 // the MFMAs (register-staged double buffering, one barrier per K block).
+#include <atomic>
 #include <cstdlib>
 #include "conv_common.h"
 
@@ -386,8 +387,27 @@ static int lin_ok(const ConvArgs& a) {
   return 2;
 }
 
+// Which kernel took each forward conv (hiseg_conv2d_path_stats, hiseg_conv2d_last_path; include/hiseg.h): conv2d_impl
+// notes the family and the variant number it passed to the *_try that launched -- for the generic kernel, the Cout
+// tile of its launch_cfg -- so a test can tell a forced variant that ran from one that declined the layer.
+static std::atomic<long long> g_conv_paths[HISEG_CONV_PATH_FAMILIES];
+static thread_local int g_conv_last = -1;
+static thread_local int g_generic_bco = 0;
+
+static void conv_note_path(int family, int variant) {
+  g_conv_paths[family].fetch_add(1);
+  g_conv_last = family * 10000 + variant;
+}
+
+// r: what a *_try returned (> 0: it launched)
+static int conv_took(int family, int variant, int r) {
+  if (r > 0) conv_note_path(family, variant);
+  return r;
+}
+
 template <typename T, typename TO, int BCO, int BPX, int WCO, int WPX>
 static int launch_cfg(const ConvArgs& a, hipStream_t s, int splits) {
+  g_generic_bco = BCO;
   dim3 grid((a.M + BPX - 1) / BPX, (a.d.Cout_pad + BCO - 1) / BCO, splits > 1 ? splits : 1);
   const size_t lds = 2u * (BCO + BPX) * 8u * 16u;
   if constexpr (sizeof(T) == 2) {
@@ -620,6 +640,25 @@ extern "C" int hiseg_conv2d_fwd_variant(const hiseg_conv2d_desc* d, int variant,
   return conv2d_impl(d, stream, variant);
 }
 
+// the generic kernel, noted as generic / generic split-K with the Cout tile it launched
+template <typename T, typename TO>
+static int launch_generic(const ConvArgs& a, hipStream_t s, int splits = 1) {
+  const int r = launch_typed<T, TO>(a, s, splits);
+  if (r == HISEG_OK) conv_note_path(splits > 1 ? HISEG_CONV_PATH_GENERIC_SPLITK : HISEG_CONV_PATH_GENERIC, g_generic_bco);
+  return r;
+}
+
+extern "C" int hiseg_conv2d_last_path(void) { return g_conv_last; }
+
+extern "C" int hiseg_conv2d_path_stats(long long* counts, int n, int reset) {
+  for (int i = 0; i < HISEG_CONV_PATH_FAMILIES; ++i) {
+    // (reset: one exchange, so a launch counted on another thread between a load and a store is not lost)
+    const long long c = reset ? g_conv_paths[i].exchange(0) : g_conv_paths[i].load();
+    if (counts && i < n) counts[i] = c;
+  }
+  return HISEG_CONV_PATH_FAMILIES;
+}
+
 static int conv2d_impl(const hiseg_conv2d_desc* d, hiseg_stream_t stream, int variant) {
   HISEG_REQUIRE(d != nullptr, HISEG_ERR_BAD_ARG, "conv2d: null descriptor");
   HISEG_REQUIRE(d->dtype == HISEG_F32 || d->dtype == HISEG_BF16, HISEG_ERR_BAD_DTYPE, "conv2d: dtype %d", d->dtype);
@@ -670,7 +709,8 @@ static int conv2d_impl(const hiseg_conv2d_desc* d, hiseg_stream_t stream, int va
     a.Ws = d->W / d->a_up;
     HISEG_REQUIRE(conv_hwc_stats_tiles(a) > 0, HISEG_ERR_BAD_ARG,
                   "conv2d: stats_partial / bnb_partial set but the layer has no fused kernel (hiseg_conv2d_stats_tiles)");
-    const int r = conv_hwc_try(a, (hipStream_t)stream, d->Cout % 128 == 0 ? 104 : 107);
+    const int sv = d->Cout % 128 == 0 ? 104 : 107;
+    const int r = conv_took(HISEG_CONV_PATH_HWC, sv, conv_hwc_try(a, (hipStream_t)stream, sv));
     HISEG_REQUIRE(r != 0, HISEG_ERR_BAD_ARG, "conv2d: the fused-statistics kernel declined the layer");
     return r < 0 ? r : HISEG_OK;
   }
@@ -749,8 +789,9 @@ static int conv2d_impl(const hiseg_conv2d_desc* d, hiseg_stream_t stream, int va
   // The fused operands of round 7 exist in one kernel each, and no other kernel may take the layer and silently
   // ignore them: the caller asks hiseg_conv2d_fused_ok first.
   if (has_fused_operands(d)) {
-    const int r = d->px_scale ? conv_pw_try(a, s, 90)
-                              : conv_hwc_try(a, s, variant ? variant : hwc_r3_mode() ? 108 : 104);
+    const int fv = variant ? variant : hwc_r3_mode() ? 108 : 104;
+    const int r = d->px_scale ? conv_took(HISEG_CONV_PATH_PW, 90, conv_pw_try(a, s, 90))
+                              : conv_took(HISEG_CONV_PATH_HWC, fv, conv_hwc_try(a, s, fv));
     HISEG_REQUIRE(r != 0, HISEG_ERR_BAD_ARG,
                   "conv2d: no kernel takes this layer with px_scale / head2_out / a_gate / res_gate "
                   "(hiseg_conv2d_fused_ok)");
@@ -763,36 +804,36 @@ static int conv2d_impl(const hiseg_conv2d_desc* d, hiseg_stream_t stream, int va
         !(variant == 0 && conv_pw_applies(a))) {
       a.kper = (a.nK + sp - 1) / sp;
       const int spl = (a.nK + a.kper - 1) / a.kper;
-      return d->out_dtype == HISEG_BF16 ? launch_typed<bf16_t, bf16_t>(a, s, spl) : launch_typed<bf16_t, float>(a, s, spl);
+      return d->out_dtype == HISEG_BF16 ? launch_generic<bf16_t, bf16_t>(a, s, spl) : launch_generic<bf16_t, float>(a, s, spl);
     }
     HISEG_REQUIRE(variant == 0, HISEG_ERR_BAD_ARG, "conv2d: variant 99 (split-K) does not apply to this layer / workspace");
   }
   if (variant == 98) {
-    const int r = conv_rows_try(a, s, variant);
+    const int r = conv_took(HISEG_CONV_PATH_ROWS, variant, conv_rows_try(a, s, variant));
     if (r != 0) return r < 0 ? r : HISEG_OK;
   } else if (variant == 90 || (variant >= 190 && variant < 222)) {
-    const int r = conv_pw_try(a, s, variant);
+    const int r = conv_took(HISEG_CONV_PATH_PW, variant, conv_pw_try(a, s, variant));
     if (r != 0) return r < 0 ? r : HISEG_OK;
   } else if ((variant >= 92 && variant <= 97) || variant == 100 || variant == 101 || (variant >= 110 && variant < 142)) {
-    const int r = conv_hwr_try(a, s, variant);
+    const int r = conv_took(HISEG_CONV_PATH_HWR, variant, conv_hwr_try(a, s, variant));
     if (r != 0) return r < 0 ? r : HISEG_OK;
   } else if (variant == 102 || (variant >= 104 && variant <= 109) || (variant >= 150 && variant < 4300)) {
-    const int r = conv_hwc_try(a, s, variant);
+    const int r = conv_took(HISEG_CONV_PATH_HWC, variant, conv_hwc_try(a, s, variant));
     if (r != 0) return r < 0 ? r : HISEG_OK;
   } else if (variant == 103) {
-    const int r = conv_hwt_try(a, s, variant);
+    const int r = conv_took(HISEG_CONV_PATH_HWT, variant, conv_hwt_try(a, s, variant));
     if (r != 0) return r < 0 ? r : HISEG_OK;
   } else if (variant >= 80 && variant < 90) {
-    const int r = conv_hw_try(a, s, variant);
+    const int r = conv_took(HISEG_CONV_PATH_HW, variant, conv_hw_try(a, s, variant));
     if (r != 0) return r < 0 ? r : HISEG_OK;
   } else if (variant >= 70 && variant < 80) {
-    const int r = conv_wide_try(a, s, variant);
+    const int r = conv_took(HISEG_CONV_PATH_WIDE, variant, conv_wide_try(a, s, variant));
     if (r != 0) return r < 0 ? r : HISEG_OK;
   } else if (variant >= 60 && variant < 70) {
-    const int r = conv_fast_try(a, s, variant);
+    const int r = conv_took(HISEG_CONV_PATH_FAST, variant, conv_fast_try(a, s, variant));
     if (r != 0) return r < 0 ? r : HISEG_OK;
   } else if (variant >= 50) {
-    const int r = conv_small_try(a, s, variant);
+    const int r = conv_took(HISEG_CONV_PATH_SMALL, variant, conv_small_try(a, s, variant));
     if (r != 0) return r < 0 ? r : HISEG_OK;
   } else if (variant >= 0) {
     int v = variant;
@@ -816,20 +857,20 @@ static int conv2d_impl(const hiseg_conv2d_desc* d, hiseg_stream_t stream, int va
     // tools/conv_bench.py: 0.205 vs 0.308 ms on 256->256 @64x48 x256 ROIs, 0.21 vs 0.34 ms on the 256+8
     // combiner, 0.16 vs 0.24 ms on 128->256; bit-identical)
     if (v == 0 && d->KH == 1 && d->KW == 1) {
-      const int r = conv_pw_try(a, s, 90);
+      const int r = conv_took(HISEG_CONV_PATH_PW, 90, conv_pw_try(a, s, 90));
       if (r != 0) return r < 0 ? r : HISEG_OK;
     }
     // narrow 3x3 layers (16 / 32 output channels: the full-image UNet's last decoder blocks and head): the
     // row-streaming kernel (conv_rows.hip, variant 98: weights in registers, input rows streamed through an LDS
     // ring; bit-identical to conv_small)
     if (v == 0 && d->KH == 3 && d->KW == 3 && d->Cout_pad <= 32) {
-      const int r = conv_rows_try(a, s, 98);
+      const int r = conv_took(HISEG_CONV_PATH_ROWS, 98, conv_rows_try(a, s, 98));
       if (r != 0) return r < 0 ? r : HISEG_OK;
       // (sources far apart in memory: conv_rows takes them through one buffer resource each, VERDICT r3 weak #1.)
       // A layer of its form it still declines (an output alignment it does not store) takes conv_small, whose
       // accumulation order is conv_rows' (bit-identical)
       if (conv_rows_form(a)) {
-        const int r2 = conv_small_try(a, s, 0);
+        const int r2 = conv_took(HISEG_CONV_PATH_SMALL, 0, conv_small_try(a, s, 0));
         if (r2 != 0) return r2 < 0 ? r2 : HISEG_OK;
       }
     }
@@ -848,51 +889,53 @@ static int conv2d_impl(const hiseg_conv2d_desc* d, hiseg_stream_t stream, int va
     // Round 6: variants 109 / 102, multi-tile workgroups (conv_hwc_mt_kernel: the next tile's first halo slice lands
     // during the last slice, two-half epilogue; bit-identical; HISEG_CONV_HWC_MTW=0|1 overrides the default)
     if (v == 0 && !four_waves && halo && d->weight_frag != nullptr && d->Cout % 128 == 0 && hwc_mt_mode(128)) {
-      const int r = conv_hwc_try(a, s, 109);
+      const int r = conv_took(HISEG_CONV_PATH_HWC, 109, conv_hwc_try(a, s, 109));
       if (r != 0) return r < 0 ? r : HISEG_OK;
     }
     if (v == 0 && !four_waves && halo && d->weight_frag != nullptr && d->Cout % 128 == 0) {
-      const int r = conv_hwc_try(a, s, hwc_r3_mode() ? 108 : 104);
+      const int cv = hwc_r3_mode() ? 108 : 104;
+      const int r = conv_took(HISEG_CONV_PATH_HWC, cv, conv_hwc_try(a, s, cv));
       if (r != 0) return r < 0 ? r : HISEG_OK;
     }
     if (v == 0 && !four_waves && halo && d->weight_frag != nullptr && d->Cout % 128 == 0) {
-      const int r = conv_hwr_try(a, s, 97);
+      const int r = conv_took(HISEG_CONV_PATH_HWR, 97, conv_hwr_try(a, s, 97));
       if (r != 0) return r < 0 ? r : HISEG_OK;
     }
     // 64-multiple Cout (the EnhancedUNet's 64-channel layers, the smp decoder's 64-channel block): conv_hwc on 64-Cout
     // x 16 x 32-pixel tiles (variant 107, round 5), else conv_hwr's (variant 100)
     if (v == 0 && !four_waves && halo && d->weight_frag != nullptr && d->Cout % 64 == 0 && hwc64_mode() &&
         hwc_mt_mode(64)) {
-      const int r = conv_hwc_try(a, s, 102);
+      const int r = conv_took(HISEG_CONV_PATH_HWC, 102, conv_hwc_try(a, s, 102));
       if (r != 0) return r < 0 ? r : HISEG_OK;
     }
     if (v == 0 && !four_waves && halo && d->weight_frag != nullptr && d->Cout % 64 == 0 && hwc64_mode()) {
-      const int r = conv_hwc_try(a, s, 107);
+      const int r = conv_took(HISEG_CONV_PATH_HWC, 107, conv_hwc_try(a, s, 107));
       if (r != 0) return r < 0 ? r : HISEG_OK;
     }
     if (v == 0 && !four_waves && halo && d->weight_frag != nullptr && d->Cout % 64 == 0) {
-      const int r = conv_hwr_try(a, s, 100);
+      const int r = conv_took(HISEG_CONV_PATH_HWR, 100, conv_hwr_try(a, s, 100));
       if (r != 0) return r < 0 ? r : HISEG_OK;
     }
     if (v == 0 && !four_waves && halo) {
       // (BCO 64 for every Cout that is not a 128 multiple: full 64 tiles plus a partial last tile)
-      const int r = conv_hw_try(a, s, d->Cout % 128 ? 89 : 86);
+      const int hv = d->Cout % 128 ? 89 : 86;
+      const int r = conv_took(HISEG_CONV_PATH_HW, hv, conv_hw_try(a, s, hv));
       if (r != 0) return r < 0 ? r : HISEG_OK;
     }
     if (v == 0 && d->Cout % 256 == 0 && d->KH * d->KW > 1 && !four_waves) {
-      const int r = conv_wide_try(a, s, 70);
+      const int r = conv_took(HISEG_CONV_PATH_WIDE, 70, conv_wide_try(a, s, 70));
       if (r != 0) return r < 0 ? r : HISEG_OK;
     }
     if (v == 0) v = four_waves ? ((d->Cout_pad % 128 == 0) ? 66 : 67) : ((d->Cout_pad % 128 == 0) ? 61 : 68);
-    const int r = conv_fast_try(a, s, v);
+    const int r = conv_took(HISEG_CONV_PATH_FAST, v, conv_fast_try(a, s, v));
     if (r != 0) return r < 0 ? r : HISEG_OK;
     if (variant == 0) {   // narrow / ragged layers: halo-tiled direct kernel
-      const int r2 = conv_small_try(a, s, 0);
+      const int r2 = conv_took(HISEG_CONV_PATH_SMALL, 0, conv_small_try(a, s, 0));
       if (r2 != 0) return r2 < 0 ? r2 : HISEG_OK;
     }
   }
   if (d->dtype == HISEG_BF16) {
-    return d->out_dtype == HISEG_BF16 ? launch_typed<bf16_t, bf16_t>(a, s) : launch_typed<bf16_t, float>(a, s);
+    return d->out_dtype == HISEG_BF16 ? launch_generic<bf16_t, bf16_t>(a, s) : launch_generic<bf16_t, float>(a, s);
   }
-  return d->out_dtype == HISEG_BF16 ? launch_typed<float, bf16_t>(a, s) : launch_typed<float, float>(a, s);
+  return d->out_dtype == HISEG_BF16 ? launch_generic<float, bf16_t>(a, s) : launch_generic<float, float>(a, s);
 }

@@ -294,6 +294,8 @@ def _declare(lib):
         "hiseg_conv2d_fwd": ([ctypes.POINTER(Conv2dDesc), P], c_int),
         "hiseg_conv2d_fwd_variant": ([ctypes.POINTER(Conv2dDesc), c_int, P], c_int),
         "hiseg_conv2d_workspace_bytes": ([ctypes.POINTER(Conv2dDesc)], c_ll),
+        "hiseg_conv2d_last_path": ([], c_int),
+        "hiseg_conv2d_path_stats": ([ctypes.POINTER(c_ll), c_int, c_int], c_int),
         "hiseg_maxpool2x2_fwd": ([c_int, P, c_int, c_int, c_int, c_int, P, P], c_int),
         "hiseg_attn_spatial_fwd": ([c_int, P, c_int, c_int, c_int, c_int, P, c_int, P, P, P, P], c_int),
         "hiseg_attn_map_fwd": ([c_int, P, c_int, c_int, c_int, c_int, P, c_int, P, P, P], c_int),
@@ -516,6 +518,24 @@ def wgrad_path_stats(reset: bool = False) -> dict:
     c = (c_ll * 5)()
     check(lib().hiseg_wgrad_path_stats(c, int(reset)), "wgrad_path_stats")
     return dict(zip(WGRAD_PATHS, (int(v) for v in c)))
+
+
+CONV_PATHS = ("generic", "generic_splitk", "fast", "wide", "hw", "hwr", "hwt", "hwc", "pw", "small", "rows")
+
+
+def conv_last_path():
+    """(family, variant) of this thread's last forward conv launch (include/hiseg.h), None before any: the kernel
+    family of CONV_PATHS and the variant number its kernel ran as (the generic families: the Cout tile, 16..128)."""
+    v = lib().hiseg_conv2d_last_path()
+    return None if v < 0 else (CONV_PATHS[v // 10000], v % 10000)
+
+
+def conv_path_stats(reset: bool = False) -> dict:
+    """How many forward conv launches each kernel family took since the last reset (include/hiseg.h)."""
+    c = (c_ll * len(CONV_PATHS))()
+    n = lib().hiseg_conv2d_path_stats(c, len(CONV_PATHS), int(reset))
+    assert n == len(CONV_PATHS), n
+    return dict(zip(CONV_PATHS, (int(v) for v in c)))
 
 
 def stream_ptr(device=None) -> int:

@@ -198,6 +198,28 @@ int hiseg_conv2d_stats_tiles(const hiseg_conv2d_desc* d);
  * hiseg_conv2d_fwd), k > 0 selects pipelined-kernel configuration k when the layer qualifies
  * (99: the split-K generic kernel; it needs the workspace and fails when the layer does not split). */
 int hiseg_conv2d_fwd_variant(const hiseg_conv2d_desc* d, int variant, hiseg_stream_t stream);
+/* Which kernel took a forward conv.  A path is family * 10000 + variant: the kernel family below and the variant
+ * number the dispatch passed to that family's kernel when it launched (for the two generic families: the Cout tile
+ * of the launch, 16 / 32 / 64 / 128).  A forced variant whose kernel declines the layer runs -- and reports -- the
+ * generic kernel.
+ * hiseg_conv2d_last_path: the path of this thread's last forward conv launch (-1 before any); a call the library
+ * split into image ranges reports its last range.
+ * hiseg_conv2d_path_stats: launches per family since the last reset, process-wide (one per image range), the first
+ * n of them into counts (null: none); reset != 0 clears them; returns HISEG_CONV_PATH_FAMILIES. */
+#define HISEG_CONV_PATH_GENERIC 0
+#define HISEG_CONV_PATH_GENERIC_SPLITK 1
+#define HISEG_CONV_PATH_FAST 2
+#define HISEG_CONV_PATH_WIDE 3
+#define HISEG_CONV_PATH_HW 4
+#define HISEG_CONV_PATH_HWR 5
+#define HISEG_CONV_PATH_HWT 6
+#define HISEG_CONV_PATH_HWC 7
+#define HISEG_CONV_PATH_PW 8
+#define HISEG_CONV_PATH_SMALL 9
+#define HISEG_CONV_PATH_ROWS 10
+#define HISEG_CONV_PATH_FAMILIES 11
+int hiseg_conv2d_last_path(void);
+int hiseg_conv2d_path_stats(long long* counts, int n, int reset);
 
 /* MaxPool2d(2) on NHWC (hierarchical_segmentation_unet.py:331-332,391).
  * in [N, H, W, C] (cstride == C), out [N, H/2, W/2, C]. */

@@ -150,6 +150,47 @@ def test_conv_transpose_and_in_scale(dt):
     assert _rel(y, ref) < (2e-5 if dt == torch.float32 else 1e-2)
 
 
+# Which kernel ran.  A forced variant whose kernel declines the layer falls through to the generic kernel, and a
+# comparison with the generic kernel then compares it with itself: after every forced call the tests below read the
+# path the library recorded (hiseg._lib.conv_last_path) and require the family the variant belongs to in
+# conv2d_impl's chain (csrc/conv_igemm.hip) -- or, for a pair listed in a DECLINES set, the generic kernel.
+def _family(v):
+    if v == 98:
+        return "rows"
+    if v == 90:
+        return "pw"
+    if 92 <= v <= 97 or v in (100, 101):
+        return "hwr"
+    if v == 102 or 104 <= v <= 109:
+        return "hwc"
+    if v == 103:
+        return "hwt"
+    if 80 <= v < 90:
+        return "hw"
+    if 70 <= v < 80:
+        return "wide"
+    if 60 <= v < 70 or 1 <= v <= 8:      # (1..8: the ring kernel's first tile forms)
+        return "fast"
+    if 50 <= v < 60:
+        return "small"
+    raise ValueError(v)
+
+
+def _ran(v, what="", declined=False, auto=None):
+    """The path of the conv2d call just made with variant `v`; `auto`: what the automatic choice (0) must report."""
+    from hiseg import _lib as L
+    path = L.conv_last_path()
+    if v == 0:
+        want = auto
+    elif v == -1 or declined:
+        want = "generic"
+    elif v == 99:
+        want = "generic_splitk"
+    else:
+        want = (_family(v), v)
+    assert want is None or path == want or path[0] == want, f"{what} variant {v}: ran {path}, expected {want}"
+
+
 # Every tap-major bf16 kernel variant must reproduce the generic kernel bit for bit: same K order per
 # accumulator, same fp32 epilogue.  name: (N, Ca, Cb, Cout, H, W, k, convT, residual, mul, out2)
 VARIANT_CASES = {
@@ -174,6 +215,50 @@ VARIANT_CASES = {
     "1x1_128_to_256": (2, 128, 0, 256, 9, 7, 1, False, False, False, False),
     "1x1_256+8_combiner": (2, 256, 8, 256, 9, 7, 1, False, False, False, False),
     "convT_256_to_128": (2, 256, 0, 128, 5, 7, 1, True, False, False, False),
+}
+
+
+_FAST128 = (1, 2, 4, 6, 61, 62, 66, 69)      # the ring kernel's 128-column tiles
+_FAST256 = (5, 7)
+_FAST = _FAST128 + _FAST256 + (3, 8, 67, 68)
+_WIDE = (70, 71, 72)
+# (case, variants) the kernel declines, by the rule of its *_try that refuses the layer
+VARIANT_DECLINES = {
+    # conv_wide_try: `d.mul != nullptr`; pw_plan: `d.KH != 1`
+    "3x3_256_res_mul_out2": _WIDE + (90,),
+    # conv_fast_try case 5 / 7 and conv_wide_try case 70 / 71: `d.Cout_pad % 256` / `d.Cout % 256`; pw_plan: `d.KH != 1`
+    "3x3_128+128": _FAST256 + (70, 71, 90),
+    # conv_fast_try: `d.Cout_pad % 128` (64 columns: the 64-column tiles 3 / 8 / 67 / 68 take it); conv_wide_try:
+    # `d.Cout & 127`; pw_plan: `d.KH != 1`
+    "3x3_64_ragged": _FAST128 + _FAST256 + _WIDE + (90,),
+    # Cout_pad 128: conv_fast_try `d.Cout_pad % 256`; conv_wide_try: `d.Cout & 127` (Cout 120)
+    "1x1_256_cout120": _FAST256 + _WIDE,
+    # conv_wide_try: `d.out2 != nullptr`; pw_plan: `d.KH != 1`
+    "3x3_128_cout250": _WIDE + (90,),
+    # conv_wide_try: `d.convT`
+    "convT_128_to_64": _WIDE,
+    # conv_wide_try: `d.convT`; pw_plan: `d.convT && d.residual`
+    "convT_256_to_128_res": _WIDE + (90,),
+    # conv_fast_try / conv_wide_try: `d.Ca % 64 != 0` (96 channels)
+    "1x1_96_to_112_overhang": _FAST + _WIDE,
+    # conv_fast_try / conv_wide_try: `d.Ca % 64 != 0` (40 channels); pw_plan: `d.KH != 1`
+    "3x3_40_to_240_overhang": _FAST + _WIDE + (90,),
+    # conv_wide_try: `d.Cb % 64 != 0`; pw_plan: `if (d.out2)`
+    "1x1_256+8_combiner_tail": _WIDE + (90,),
+    # conv_fast_try: `d.Cout_pad % 128` (64 columns); conv_wide_try: `d.Cb % 64 != 0`; pw_plan: narrow tiles are
+    # single-source (`comb ? ... : d.Cb != 0`)
+    "1x1_128+40_tail_cout64": _FAST128 + _FAST256 + _WIDE + (90,),
+    "3x3_256_res_ragged": (90,),           # pw_plan: `d.KH != 1`
+    "3x3_128+128_to_256": (90,),           # pw_plan: `d.KH != 1`
+    # Cout 128: conv_fast_try `d.Cout_pad % 256`, conv_wide_try case 70 / 71 `d.Cout % 256`
+    "1x1_256_to_128_res": _FAST256 + (70, 71),
+    "3x3_256_smp_decoder0_30x40": (90,),   # pw_plan: `d.KH != 1`
+    "1x1_256_to_256_res_ragged": (),
+    "1x1_128_to_256": (),
+    # conv_wide_try: `d.Cb % 64 != 0`; pw_plan: `(rb > 4 && nks > 8)` refuses 256-column tiles at 9 k-steps before
+    # the 256 + 8 combiner form below it is reached (no layer reaches that form: it runs on the ring kernel)
+    "1x1_256+8_combiner": _WIDE + (90,),
+    "convT_256_to_128": _WIDE,             # conv_wide_try: `d.convT`
 }
 
 
@@ -203,6 +288,7 @@ def test_conv_kernel_variants_bit_identical(name):
     for v in (-1, 1, 2, 3, 4, 5, 6, 7, 8, 61, 62, 66, 67, 68, 69, 70, 71, 72, 90):
         o2a = ops.Act.new(N, oH, oW, Cout, dt, DEV) if o2 else None
         y = ops.conv2d(p, xa, xb, residual=R, mul=M, out2=o2a, variant=v)
+        _ran(v, name, declined=v in VARIANT_DECLINES[name])
         torch.cuda.synchronize()
         outs[v] = (y.t.clone(), None if o2a is None else o2a.t.clone())
     ref, ref2 = outs[-1]
@@ -227,8 +313,11 @@ def test_conv_pointwise_gate_mul_bit_identical(shape, act):
     p = ops.pack_conv(w, torch.randn(Cout, device=DEV, generator=g) * 0.1, None, act, dt, DEV, pad=0)
     m = ops.Act.from_nchw(torch.randn(N, Cout, H, W, device=DEV, generator=g), dt)
     ref = ops.conv2d(p, x, mul=m, variant=-1).t.clone()
+    _ran(-1)
     y = ops.conv2d(p, x, mul=m, variant=90).t.clone()
+    _ran(90)
     auto = ops.conv2d(p, x, mul=m, variant=0).t.clone()
+    _ran(0, auto=("pw", 90))     # (a 1x1 layer: the pointwise kernel is the chain's first try)
     torch.cuda.synchronize()
     assert torch.isfinite(ref.float()).all()
     assert torch.equal(y, ref) and torch.equal(auto, ref)
@@ -247,6 +336,11 @@ NARROW_CASES = {
     "3x3_8_to_64": (2, 8, 0, 64, 9, 13, 3, 1, False, False, False, False),
     "3x3_64+8_to_64_ins": (2, 64, 8, 64, 6, 7, 3, 1, True, False, True, False),
 }
+
+
+# pick_th (csrc/conv_small.hip): `lds_for(th) > 160 * 1024` -- the weights plus 8 + 2 halo rows of 66 columns pass the
+# LDS at 8 rows per workgroup: 96 channels x 32 columns 57 856 + 137 280 bytes, 72 x 64 91 136 + 95 040
+NARROW_DECLINES = {("up2_64+32_to_32", 58), ("3x3_64+8_to_64_ins", 58)}
 
 
 @pytest.mark.parametrize("name", list(NARROW_CASES))
@@ -268,6 +362,7 @@ def test_conv_small_kernel_bit_identical(name):
         o2 = ops.Act.new(N, H, W, Cout, dt, DEV) if mul else None
         y = ops.conv2d(p, xa, xb, a_up=up, residual=R, mul=M, out2=o2, in_scale=gate,
                        out_dtype=torch.float32 if f32o else None, variant=v)
+        _ran(v, name, declined=(name, v) in NARROW_DECLINES)
         torch.cuda.synchronize()
         outs[v] = (y.t.clone(), None if o2 is None else o2.t.clone())
     ref, ref2 = outs[-1]
@@ -308,6 +403,7 @@ def test_conv_rows_bit_identical(name):
     outs = {}
     for v in (-1, 50, 98, 0):
         y = ops.conv2d(p, xa, xb, a_up=up, out_dtype=torch.float32 if f32o else None, variant=v)
+        _ran(v, name, auto=("rows", 98))   # (3x3 with <= 32 output columns: conv_rows is the chain's first try)
         torch.cuda.synchronize()
         outs[v] = y.t.clone()
     assert torch.isfinite(outs[-1].float()).all()
@@ -329,7 +425,9 @@ def test_conv_small_stride2_bit_identical(shape):
     filler.fill_module(bn)
     p = ops.pack_conv(w, None, bn, 3, dt, DEV, stride=2, pad=1)
     ref = ops.conv2d(p, x, variant=-1).t.clone()
+    _ran(-1)
     auto = ops.conv2d(p, x, variant=0).t.clone()
+    _ran(0, auto=("small", 0))   # (stride 2: no rows / halo / ring kernel takes it; conv_small's stride-2 form does)
     torch.cuda.synchronize()
     assert torch.isfinite(ref.float()).all()
     assert torch.equal(auto, ref)
@@ -376,6 +474,7 @@ def test_conv_pointwise_efficientnet_bit_identical(name):
     outs = {}
     for v in (-1, 0, 90):
         y = ops.conv2d(p, xa, residual=R, in_scale=gate, variant=v)
+        _ran(v, name, auto=("pw", 90))
         torch.cuda.synchronize()
         outs[v] = y.t.clone()
     assert torch.isfinite(outs[-1].float()).all()
@@ -455,6 +554,7 @@ def test_conv_splitk_within_reassociation(name):
     outs = {}
     for v in (-1, 99, 0, "again"):
         y = ops.conv2d(p, xa, residual=R, in_scale=gate, variant=0 if v == "again" else v)
+        _ran(0 if v == "again" else v, name, auto="generic_splitk")
         torch.cuda.synchronize()
         outs[v] = y.to_nchw().float()
     assert torch.equal(outs[0], outs[99]) and torch.equal(outs[0], outs["again"])
@@ -685,6 +785,13 @@ def test_stream_pipelined_export_matches_serial(gate):
         assert torch.equal(a, c) and torch.equal(b, d)
 
 
+# Variant 74 here (residual only, no mul / out2): conv_wide_try's `d.Cout % 256` (case 74), `d.Ca % 64 != 0` /
+# `d.Cb % 64 != 0` (the 96- / 40-channel sources, the 8- / 40-channel tails)
+WIDE74_DECLINES = {"3x3_128+128", "3x3_64_ragged", "1x1_256_cout120", "3x3_128_cout250", "1x1_96_to_112_overhang",
+                   "3x3_40_to_240_overhang", "1x1_256+8_combiner_tail", "1x1_128+40_tail_cout64",
+                   "1x1_256_to_128_res", "1x1_256+8_combiner"}
+
+
 @pytest.mark.parametrize("name", list(VARIANT_CASES))
 def test_conv_wide_channel_major_variant_within_bf16(name):
     """Variant 74: the wide-tile kernel with the channel-major K order (the 9 taps of a 32-channel slice back
@@ -704,6 +811,7 @@ def test_conv_wide_channel_major_variant_within_bf16(name):
     R = ops.Act.from_nchw(torch.randn(N, Cout, H, W, device=DEV, generator=g), dt) if res else None
     ref = ops.conv2d(p, xa, xb, residual=R, variant=-1).to_nchw().float()
     y = ops.conv2d(p, xa, xb, residual=R, variant=74).to_nchw().float()
+    _ran(74, name, declined=name in WIDE74_DECLINES)
     assert torch.isfinite(y).all()
     assert ((y - ref).abs().max() / ref.abs().max()).item() < 8e-3
 
@@ -940,7 +1048,9 @@ def test_conv_halo_wide_within_bf16(name, variant):
     p = ops.pack_conv(w, torch.randn(Cout, device=DEV, generator=g) * 0.1, None, int(relu), dt, DEV, pad=1)
     R = ops.Act.from_nchw(torch.randn(N, Cout, H, W, device=DEV, generator=g), dt) if res else None
     ref = ops.conv2d(p, xa, residual=R, variant=-1).to_nchw().float()
+    _ran(-1)
     y = ops.conv2d(p, xa, residual=R, variant=variant).to_nchw().float()
+    _ran(variant, name)
     torch.cuda.synchronize()
     assert torch.isfinite(y).all()
     assert ((y - ref).abs().max() / ref.abs().max()).item() < 8e-3
@@ -965,17 +1075,21 @@ def test_conv_hwr_bit_identical_to_halo_kernel(name):
     p = ops.pack_conv(w, torch.randn(Cout, device=DEV, generator=g) * 0.1, None, int(relu), dt, DEV, pad=1)
     assert p.weight_frag is not None
     R = ops.Act.from_nchw(torch.randn(N, Cout, H, W, device=DEV, generator=g), dt) if res else None
-    y82 = ops.conv2d(p, xa, residual=R, variant=82).t.clone()
-    y86 = ops.conv2d(p, xa, residual=R, variant=86).t.clone()
-    ys = {v: ops.conv2d(p, xa, residual=R, variant=v).t.clone() for v in (92, 93, 94, 95, 96, 97)}
-    auto = ops.conv2d(p, xa, residual=R, variant=0).t.clone()
+    def run(v, auto=None):
+        y = ops.conv2d(p, xa, residual=R, variant=v).t.clone()
+        _ran(v, name, auto=auto)
+        return y
+    y82, y86 = run(82), run(86)
+    ys = {v: run(v) for v in (92, 93, 94, 95, 96, 97)}
+    # the automatic choice: conv_hwc's ring-of-three form (variant 108, round 6), bit-identical to 97 / 104 by design
+    auto = run(0, auto=("hwc", 108))
     torch.cuda.synchronize()
     assert torch.isfinite(ys[92].float()).all()
     for v in (92, 93, 94, 95):    # ky-major taps: variant 82's accumulation order
         assert torch.equal(ys[v], y82), v
     for v in (96, 97):            # kx-major taps with B reuse: variant 86's
         assert torch.equal(ys[v], y86), v
-    assert torch.equal(auto, ys[97])   # the automatic choice takes variant 97
+    assert torch.equal(auto, ys[97])   # (variant 108's accumulation order is variant 97's)
 
 
 @pytest.mark.parametrize("shape", [(2, 64, 0, 64, 64, 48, True), (3, 64, 0, 64, 21, 37, False), (2, 128, 0, 64, 16, 33, True),
@@ -984,7 +1098,8 @@ def test_conv_hwr_bit_identical_to_halo_kernel(name):
 def test_conv_hwr_wide_tile_bit_identical(shape):
     """Variants 100 (64-Cout x 16 x 32-pixel tiles, four waves) and 101 (128-Cout x 16 x 32, eight waves): the same
     per-element accumulation order as variant 97 / conv_hw's 86 and 89 (channel-major slices, kx-major taps) -- bit
-    for bit, ragged pixel tiles, residual, two sources; the automatic choice on 64-channel layers takes 100."""
+    for bit, ragged pixel tiles, residual, two sources; the automatic choice takes conv_hwc's forms of the same order
+    (108 for 128-multiple Cout, 107 for the other 64-multiples)."""
     from hiseg import ops
     N, Ca, Cb, Cout, H, W, res = shape
     dt = torch.bfloat16
@@ -996,12 +1111,14 @@ def test_conv_hwr_wide_tile_bit_identical(shape):
                       split=(Ca, Cb) if Cb else None)
     assert p.weight_frag is not None
     R = ops.Act.from_nchw(torch.randn(N, Cout, H, W, device=DEV, generator=g), dt) if res else None
-    y100 = ops.conv2d(p, xa, xb, residual=R, variant=100).t.clone()
-    ref = ops.conv2d(p, xa, xb, residual=R, variant=89).t.clone()
-    auto = ops.conv2d(p, xa, xb, residual=R, variant=0).t.clone()
+    def run(v, auto=None):
+        y = ops.conv2d(p, xa, xb, residual=R, variant=v).t.clone()
+        _ran(v, str(shape), auto=auto)
+        return y
+    y100, ref = run(100), run(89)
+    auto = run(0, auto=("hwc", 108 if Cout % 128 == 0 else 107))
     if Cout % 128 == 0:
-        y97 = ops.conv2d(p, xa, xb, residual=R, variant=97).t.clone()
-        y101 = ops.conv2d(p, xa, xb, residual=R, variant=101).t.clone()
+        y97, y101 = run(97), run(101)
     torch.cuda.synchronize()
     assert torch.isfinite(y100.float()).all()
     assert torch.equal(y100, ref)
@@ -1026,10 +1143,11 @@ def test_conv_hwr_two_source_bit_identical(shape):
     p = ops.pack_conv(w, torch.randn(Cout, device=DEV, generator=g) * 0.1, None, 1, dt, DEV, pad=1, split=(Ca, Cb))
     assert p.weight_frag is not None
     R = ops.Act.from_nchw(torch.randn(N, Cout, H, W, device=DEV, generator=g), dt) if res else None
-    y82 = ops.conv2d(p, xa, xb, residual=R, variant=82).t.clone()
-    y92 = ops.conv2d(p, xa, xb, residual=R, variant=92).t.clone()
-    y86 = ops.conv2d(p, xa, xb, residual=R, variant=86).t.clone()
-    y97 = ops.conv2d(p, xa, xb, residual=R, variant=97).t.clone()
+    def run(v):
+        y = ops.conv2d(p, xa, xb, residual=R, variant=v).t.clone()
+        _ran(v, str(shape))
+        return y
+    y82, y92, y86, y97 = run(82), run(92), run(86), run(97)
     torch.cuda.synchronize()
     assert torch.equal(y92, y82)
     assert torch.equal(y97, y86)
@@ -1058,7 +1176,9 @@ def test_conv_halo_two_source_within_bf16(shape, variant):
                       split=(Ca, Cb) if Cb else None)
     R = ops.Act.from_nchw(torch.randn(N, Cout, H, W, device=DEV, generator=g), dt) if res else None
     ref = ops.conv2d(p, xa, xb, residual=R, variant=-1).to_nchw().float()
+    _ran(-1)
     y = ops.conv2d(p, xa, xb, residual=R, variant=variant).to_nchw().float()
+    _ran(variant, str(shape))
     auto = ops.conv2d(p, xa, xb, residual=R, variant=0).to_nchw().float()
     torch.cuda.synchronize()
     assert torch.isfinite(y).all()
@@ -1091,6 +1211,7 @@ def test_conv_halo_upsampled_decoder_within_bf16(shape):
     ref0 = ops.conv2d(p0, xa, xb, a_up=2, variant=-1).to_nchw().float()
     ref = ops.conv2d(p, xa, xbp, a_up=2, variant=-1).to_nchw().float()
     y = ops.conv2d(p, xa, xbp, a_up=2, variant=variant).to_nchw().float()
+    _ran(variant, str(shape))
     auto = ops.conv2d(p, xa, xbp, a_up=2, variant=0).to_nchw().float()
     torch.cuda.synchronize()
     assert torch.isfinite(y).all()
@@ -1164,6 +1285,7 @@ def test_conv_hwt_bit_identical_to_hwr(shape):
         o = ops.Act.new(N, H, W, Cout, dt, torch.device(DEV))
         o.t.fill_(float("nan"))
         outs[v] = ops.conv2d(p, xa, xb, out=o, residual=R, variant=v).t.clone()
+        _ran(v, str(shape), auto=("hwc", 108))
     torch.cuda.synchronize()
     assert torch.isfinite(outs[97].float()).all()
     assert torch.equal(outs[103], outs[97])
@@ -1200,6 +1322,7 @@ def test_conv_hwc_bit_identical_to_hwr(shape):
         o = ops.Act.new(N, H, W, Cout, dt, torch.device(DEV))
         o.t.fill_(float("nan"))
         outs[v] = ops.conv2d(p, xa, xb, out=o, residual=R, variant=v).t.clone()
+        _ran(v, str(shape), auto=("hwc", 108))
     torch.cuda.synchronize()
     assert torch.isfinite(outs[97].float()).all()
     for v in vs:
@@ -1230,6 +1353,7 @@ def test_conv_hwc64_bit_identical_to_hwr(shape):
         o = ops.Act.new(N, H, W, Cout, dt, torch.device(DEV))
         o.t.fill_(float("nan"))
         outs[v] = ops.conv2d(p, xa, xb, out=o, residual=R, variant=v).t.clone()
+        _ran(v, str(shape), auto=("hwc", 107))
     torch.cuda.synchronize()
     assert torch.isfinite(outs[100].float()).all()
     assert torch.equal(outs[107], outs[100]) and torch.equal(outs[0], outs[100])
@@ -1252,6 +1376,7 @@ def test_conv_hwc64_upsampled_decoder_bit_identical(shape):
         o = ops.Act.new(N, H, W, Cout, dt, torch.device(DEV))
         o.t.fill_(float("nan"))
         outs[v] = ops.conv2d(p, xa, xb, out=o, a_up=2, variant=v).t.clone()
+        _ran(v, str(shape), auto=("hwc", 107))
     torch.cuda.synchronize()
     assert torch.isfinite(outs[100].float()).all()
     assert torch.equal(outs[107], outs[100]) and torch.equal(outs[0], outs[100])
@@ -1274,6 +1399,7 @@ def test_conv_hwc_upsampled_decoder_bit_identical(shape):
         o = ops.Act.new(N, H, W, Cout, dt, torch.device(DEV))
         o.t.fill_(float("nan"))
         outs[v] = ops.conv2d(p, xa, xb, out=o, a_up=2, variant=v).t.clone()
+        _ran(v, str(shape), auto=("hwc", 108))
     torch.cuda.synchronize()
     assert torch.isfinite(outs[97].float()).all()
     assert torch.equal(outs[104], outs[97]) and torch.equal(outs[108], outs[97]) and torch.equal(outs[0], outs[97])
@@ -1427,6 +1553,7 @@ def test_conv3x3_small_image_splitk(shape):
     p = ops.pack_conv(w, b, None, 1, dt, DEV, pad=1)
     R = ops.Act.from_nchw(torch.randn(N, Co, H, W, device=DEV, generator=g), dt) if res else None
     out = ops.conv2d(p, xa, residual=R, split_k_3x3=True).to_nchw().float()
+    _ran(0, str(shape), auto="generic_splitk")
     ref = F.conv2d(x.to(dt).float(), w.to(dt).float(), b, padding=1)
     if res:
         ref = ref + R.to_nchw().float()
@@ -1434,10 +1561,12 @@ def test_conv3x3_small_image_splitk(shape):
     assert _rel(out.cpu(), ref.cpu()) < 1e-2
     if Co % 128 == 0:
         h = ops.conv2d(p, xa, residual=R, variant=97).to_nchw().float()
+        _ran(97, str(shape))
         assert _rel(out.cpu(), h.cpu()) < 1e-2
     one = ops.Act.from_nchw(x[:1].contiguous(), dt)
     R1 = ops.Act.from_nchw(R.to_nchw()[:1].contiguous(), dt) if res else None
     o1 = ops.conv2d(p, one, residual=R1, split_k_3x3=True).to_nchw()
+    _ran(0, str(shape), auto="generic_splitk")   # (one image alone splits the same way)
     assert torch.equal(o1[0], ops.conv2d(p, xa, residual=R, split_k_3x3=True).to_nchw()[0])
 
 
@@ -1481,6 +1610,7 @@ def test_igemm_linear_gather_bit_identical(name, monkeypatch):
         for lin in ("2", "0"):
             monkeypatch.setenv("HISEG_IGEMM_LIN", lin)
             y = ops.conv2d(p, xa, residual=R, in_scale=gate, variant=v, split_k_3x3=(k == 3))
+            _ran(v, name)   # (-1: the generic kernel, 99: its split-K form; the automatic choice is not pinned here)
             torch.cuda.synchronize()
             outs.append(y.to_nchw().float())
         assert torch.isfinite(outs[0]).all()
