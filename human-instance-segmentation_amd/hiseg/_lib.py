@@ -520,6 +520,12 @@ def wgrad_path_stats(reset: bool = False) -> dict:
     return dict(zip(WGRAD_PATHS, (int(v) for v in c)))
 
 
+def wgrad_last_path():
+    """The kernel of this thread's last hiseg_conv2d_wgrad (a name of WGRAD_PATHS), None before any."""
+    v = lib().hiseg_wgrad_last_path()
+    return None if v < 0 else WGRAD_PATHS[v]
+
+
 CONV_PATHS = ("generic", "generic_splitk", "fast", "wide", "hw", "hwr", "hwt", "hwc", "pw", "small", "rows")
 
 

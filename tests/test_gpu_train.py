@@ -120,11 +120,14 @@ def test_conv_backward_matches_autograd(case, dt):
         assert err(dt)(grad_nchw(T, xb), xr.grad[:, split[0]:]) < tol(dt)
 
 
-WIDE_WGRAD_CASES = [  # (cin, cout, k, H, W, N, bias, two-source split): 128-multiple GEMM columns (wgrad_wide.hip)
+# (cin, cout, k, H, W, N, bias, two-source split): 128-multiple GEMM columns with the halo tile off.  wgrad_wide_bc
+# (wgrad_wide.hip) takes a layer only when Cin % 256 == 0 and Cg % 256 == 0, one source or two near ones: the wide tile
+# runs the first three cases, conv_wgrad_tr_kernel's 128-column tile the other five (wide_wgrad_path below).
+WIDE_WGRAD_CASES = [
     (256, 256, 3, 16, 12, 2, False, None),
     (256, 256, 3, 32, 24, 4, False, None),        # many pixel splits
     (256, 256, 3, 12, 10, 2, True, None),         # bias column in the last K tile of a shared-tap layer
-    (128, 128, 3, 9, 7, 2, True, None),           # ragged K tile (1152 + bias column), C tile 128
+    (128, 128, 3, 9, 7, 2, True, None),           # transposed-read: ragged K tile (1152 + bias column), C tile 128
     (256, 128, 3, 12, 10, 2, False, None),
     (128, 256, 3, 12, 10, 3, True, None),
     (258, 256, 1, 8, 6, 2, True, (256, 2)),       # two sources + bias in one K tile
@@ -132,13 +135,28 @@ WIDE_WGRAD_CASES = [  # (cin, cout, k, H, W, N, bias, two-source split): 128-mul
 ]
 
 
+def wide_wgrad_path(case):
+    """The kernel a WIDE_WGRAD_CASES / TR_WGRAD_CASES layer takes with HISEG_WGRAD_HWC=0 (wgrad_wide_bc: Cin and Cout
+    multiples of 256; the two-source cases of these tables miss that by shape, so where the allocator put their sources
+    does not enter)."""
+    cin, cout = case[0], case[1]
+    return "wide" if cin % 256 == 0 and cout % 256 == 0 else "transposed_read"
+
+
+def assert_one_wgrad(L, path):
+    stats = L.wgrad_path_stats()
+    assert stats[path] == 1 and sum(stats.values()) == 1 and L.wgrad_last_path() == path, (path, stats)
+
+
 @pytest.mark.parametrize("reduce_taps", ["1", "0"])
 @pytest.mark.parametrize("case", WIDE_WGRAD_CASES)
 def test_wgrad_wide_matches_f64_of_bf16_operands(case, reduce_taps, monkeypatch):
-    """bf16 weight gradients of the 128-multiple-column layers (the wide-tile kernel) against float64 autograd of
+    """bf16 weight gradients of the 128-multiple-column layers (the wide tile where wide_wgrad_path says so, else the
+    transposed-read tile; the recorded path is asserted) against float64 autograd of
     the same bf16-rounded operands: the kernel's only error is its f32 accumulation, so 1e-4 of the max holds --
     with the split partials reduced by the tap-major kernel (3x3 single-source layers, coalesced reference-layout
     stores) and by the quad-of-K kernel (HISEG_WGRAD_REDUCE_TAPS=0)."""
+    from hiseg import _lib as L
     from hiseg.ops import Act
     monkeypatch.setenv("HISEG_WGRAD_REDUCE_TAPS", reduce_taps)
     monkeypatch.setenv("HISEG_WGRAD_HWC", "0")   # the transposed-read / wide tiles (the halo tile: below)
@@ -156,7 +174,10 @@ def test_wgrad_wide_matches_f64_of_bf16_operands(case, reduce_taps, monkeypatch)
     g = torch.from_numpy(filler.normal(12, (N, cout, H, W))).to(DEV)
     inject(T, y, g, dt)
     S.flat.prepare_backward()
+    L.wgrad_path_stats(reset=True)
     T.run_backward()
+    torch.cuda.synchronize()
+    assert_one_wgrad(L, wide_wgrad_path(case))
     xr = x.to(dt).double().requires_grad_(True)
     wr = conv.weight.detach().to(dt).double().requires_grad_(True)
     br = torch.zeros(cout, dtype=torch.float64, device=DEV, requires_grad=True) if bias else None
@@ -237,7 +258,8 @@ def test_wgrad_dma_addressing_bit_identical(knob, values, case, monkeypatch):
     of its two X images with and without per-stage incremental byte offsets (HISEG_WGRAD_SHT=2 / 1) vs 0, and its
     image-major ring with per-stage flipped fragment-read registers (HISEG_WGRAD_TOG=1) vs the stage-major one;
     conv_wgrad_tr_kernel: incremental offsets (HISEG_WGRAD_INC=1) vs 0 and the flipped read registers (TOG), one and
-    two sources."""
+    two sources.  Every run must record the kernel the table names: wide / transposed_read."""
+    from hiseg import _lib as L
     from hiseg.ops import Act
     monkeypatch.setenv("HISEG_WGRAD_HWC", "0")   # these knobs belong to the transposed-read / wide tiles
     cin, cout, k, H, W, N, bias, split = case
@@ -257,7 +279,10 @@ def test_wgrad_dma_addressing_bit_identical(knob, values, case, monkeypatch):
         y = TE.conv_plain(T, conv, TE.ACT_NONE, xa, xb, split=split)
         inject(T, y, g, dt)
         S.flat.prepare_backward()
+        L.wgrad_path_stats(reset=True)
         T.run_backward()
+        torch.cuda.synchronize()
+        assert_one_wgrad(L, wide_wgrad_path(case))
         grads.append((conv.weight.grad.clone(), conv.bias.grad.clone() if bias else None))
     for gw, gb in grads[1:]:
         assert torch.equal(grads[0][0], gw)
