@@ -19,6 +19,29 @@ struct ConvArgs {
   int abl = 0; // DIAG builds only: ablation bits of a timing variant (parts of a kernel switched off)
 };
 
+// ---- host interface of the forward conv kernel files (conv_dispatch.cpp chooses among them) ----
+// A family's *_try(a, s, variant): 1 = launched, 0 = the layer does not qualify (the caller falls back), < 0 = error.
+int conv_fast_try(const ConvArgs& a, hipStream_t s, int variant);
+int conv_wide_try(const ConvArgs& a, hipStream_t s, int variant);
+int conv_hw_try(const ConvArgs& a, hipStream_t s, int variant);
+int conv_hwr_try(const ConvArgs& a, hipStream_t s, int variant);
+int conv_hwt_try(const ConvArgs& a, hipStream_t s, int variant);
+int conv_hwc_try(const ConvArgs& a, hipStream_t s, int variant);
+int conv_pw_try(const ConvArgs& a, hipStream_t s, int variant);
+int conv_small_try(const ConvArgs& a, hipStream_t s, int variant);
+int conv_rows_try(const ConvArgs& a, hipStream_t s, int variant);
+// planners (no launch)
+bool conv_pw_applies(const ConvArgs& a);
+int conv_pw_gate_images(const ConvArgs& a);
+bool conv_rows_form(const ConvArgs& a);
+int conv_hwc_stats_tiles(const ConvArgs& a);
+int conv_hwc_fused_variant(const ConvArgs& a, bool r3);
+// The generic kernel (conv_igemm.hip), any dtype pair; splits > 1: its split-K form (a.kper K blocks per split, a.ws
+// the workspace).  *bco: the Cout tile it launched.  Returns a HISEG_* status.
+int conv_generic_launch(const ConvArgs& a, hipStream_t s, int splits, int* bco);
+int splitk_plan(const ConvArgs& a);                        // splits (>= 2) of the generic kernel for this layer, or 1
+long long splitk_bytes(const ConvArgs& a, int splits);     // the workspace that plan needs
+
 template <typename T>
 __device__ __forceinline__ void load4(const void* base, long long idx, bool vec, int nvalid,
                                       float* v) {

@@ -18,7 +18,8 @@
 // groups of the fragment reads (MI355X_MICROARCH.md §LDS) and for the row-wise stores.
 // Two LDS stages; the next K block is gathered into registers while the current one feeds
 // the MFMAs (register-staged double buffering, one barrier per K block).
-#include <atomic>
+//
+// This file is the generic kernel alone: conv_dispatch.cpp decides when it runs (conv_generic_launch, splitk_plan).
 #include <cstdlib>
 #include "conv_common.h"
 
@@ -387,27 +388,8 @@ static int lin_ok(const ConvArgs& a) {
   return 2;
 }
 
-// Which kernel took each forward conv (hiseg_conv2d_path_stats, hiseg_conv2d_last_path; include/hiseg.h): conv2d_impl
-// notes the family and the variant number it passed to the *_try that launched -- for the generic kernel, the Cout
-// tile of its launch_cfg -- so a test can tell a forced variant that ran from one that declined the layer.
-static std::atomic<long long> g_conv_paths[HISEG_CONV_PATH_FAMILIES];
-static thread_local int g_conv_last = -1;
-static thread_local int g_generic_bco = 0;
-
-static void conv_note_path(int family, int variant) {
-  g_conv_paths[family].fetch_add(1);
-  g_conv_last = family * 10000 + variant;
-}
-
-// r: what a *_try returned (> 0: it launched)
-static int conv_took(int family, int variant, int r) {
-  if (r > 0) conv_note_path(family, variant);
-  return r;
-}
-
 template <typename T, typename TO, int BCO, int BPX, int WCO, int WPX>
 static int launch_cfg(const ConvArgs& a, hipStream_t s, int splits) {
-  g_generic_bco = BCO;
   dim3 grid((a.M + BPX - 1) / BPX, (a.d.Cout_pad + BCO - 1) / BCO, splits > 1 ? splits : 1);
   const size_t lds = 2u * (BCO + BPX) * 8u * 16u;
   if constexpr (sizeof(T) == 2) {
@@ -457,22 +439,34 @@ static int igemm_bco(int cp) {
 // thread made a gated split workgroup several times slower (960 -> 160 over 4 x 40 x 40: 57 us)
 static int splitk_bco(int cp) { return cp >= 96 && igemm_bco(cp) == 128 ? 128 : 64; }
 
+// *bco: the Cout tile of the launch (what hiseg_conv2d_last_path reports for the generic kernel)
 template <typename T, typename TO>
-static int launch_typed(const ConvArgs& a, hipStream_t s, int splits = 1) {
+static int launch_typed(const ConvArgs& a, hipStream_t s, int splits, int* bco) {
   // SE-gated layers as the split-K ones: the narrow 16 / 32 x 256 tiles gather their gated A chunks through
   // registers (the B7's 480 -> 80 projections over 4 x 80 x 80 at 16 x 256 tiles: 66 us per launch)
   static const bool gated_wide = [] { const char* e = getenv("HISEG_GATED_WIDE"); return !(e && atoi(e) == 0); }();
+  int tile;
   if (splits > 1 || (gated_wide && a.d.in_scale != nullptr)) {
-    if (splitk_bco(a.d.Cout_pad) == 128) return launch_cfg<T, TO, 128, 128, 2, 2>(a, s, splits);
-    return launch_cfg<T, TO, 64, 128, 2, 2>(a, s, splits);
+    tile = splitk_bco(a.d.Cout_pad);
+  } else {
+    const char* eb = getenv("HISEG_IGEMM_BCO");   // A/B timing: force the Cout tile (read per call)
+    tile = eb ? atoi(eb) : igemm_bco(a.d.Cout_pad);
+    if (tile != 128 && tile != 64 && tile != 32) tile = 16;
   }
-  const char* eb = getenv("HISEG_IGEMM_BCO");   // A/B timing: force the Cout tile (read per call)
-  switch (eb ? atoi(eb) : igemm_bco(a.d.Cout_pad)) {
+  *bco = tile;
+  switch (tile) {
     case 128: return launch_cfg<T, TO, 128, 128, 2, 2>(a, s, splits);
     case 64: return launch_cfg<T, TO, 64, 128, 2, 2>(a, s, splits);
     case 32: return launch_cfg<T, TO, 32, 256, 1, 4>(a, s, splits);
     default: return launch_cfg<T, TO, 16, 256, 1, 4>(a, s, splits);
   }
+}
+
+int conv_generic_launch(const ConvArgs& a, hipStream_t s, int splits, int* bco) {
+  const bool obf = a.d.out_dtype == HISEG_BF16;
+  if (a.d.dtype == HISEG_BF16)
+    return obf ? launch_typed<bf16_t, bf16_t>(a, s, splits, bco) : launch_typed<bf16_t, float>(a, s, splits, bco);
+  return obf ? launch_typed<float, bf16_t>(a, s, splits, bco) : launch_typed<float, float>(a, s, splits, bco);
 }
 
 // Split-K plan of the generic kernel for a bf16 1x1 layer with a long K loop over a small image: splits (>= 2) or 1
@@ -482,7 +476,7 @@ static int launch_typed(const ConvArgs& a, hipStream_t s, int splits = 1) {
 // (test_c2_shape_bf16_properties_and_oracle).  Images of <= 1600 pixels (the EfficientNet's stride-16 / 32
 // stages at 640 x 640 and 480 x 640), >= 6 K blocks: nK / 4 splits, 2..8.  The workspace it needs: splits x M x
 // Cout_pad f32.
-static int splitk_plan(const ConvArgs& a) {
+int splitk_plan(const ConvArgs& a) {
   const hiseg_conv2d_desc& d = a.d;
   if (d.dtype != HISEG_BF16 || d.convT || a.nK < 6) return 1;
   // 3x3 layers over images of <= 256 pixels with long K (the B7 EnhancedUNet's 768-channel 3x3 pair over 8 x 16 x 12:
@@ -507,435 +501,8 @@ static int splitk_plan(const ConvArgs& a) {
   return sp >= 2 ? sp : 2;
 }
 
-static long long splitk_bytes(const ConvArgs& a, int splits) {
+long long splitk_bytes(const ConvArgs& a, int splits) {
   return splits > 1 ? (long long)splits * a.M * a.d.Cout_pad * 4 : 0;
 }
 
 }  // namespace hiseg
-
-namespace hiseg {
-int conv_fast_try(const ConvArgs& a, hipStream_t s, int variant);
-int conv_wide_try(const ConvArgs& a, hipStream_t s, int variant);
-int conv_hw_try(const ConvArgs& a, hipStream_t s, int variant);
-int conv_pw_try(const ConvArgs& a, hipStream_t s, int variant);
-int conv_hwr_try(const ConvArgs& a, hipStream_t s, int variant);
-int conv_hwt_try(const ConvArgs& a, hipStream_t s, int variant);
-int conv_hwc_try(const ConvArgs& a, hipStream_t s, int variant);
-int conv_hwc_stats_tiles(const ConvArgs& a);
-int conv_hwc_fused_variant(const ConvArgs& a, bool r3);
-int conv_small_try(const ConvArgs& a, hipStream_t s, int variant);
-int conv_rows_try(const ConvArgs& a, hipStream_t s, int variant);
-bool conv_pw_applies(const ConvArgs& a);
-int conv_pw_gate_images(const ConvArgs& a);
-bool conv_rows_form(const ConvArgs& a);
-}
-
-using namespace hiseg;
-
-
-static int conv2d_impl(const hiseg_conv2d_desc* d, hiseg_stream_t stream, int variant);
-
-extern "C" int hiseg_conv2d_fwd(const hiseg_conv2d_desc* d, hiseg_stream_t stream) {
-  return conv2d_impl(d, stream, 0);
-}
-
-// The variants a release library accepts: the automatic choice, the generic kernel and every configuration
-// tests/test_gpu_parity.py checks bit for bit.  Timing-only, stamp and experimental kernels exist only in a
-// -DHISEG_DIAG build (Makefile DIAG=1).
-// HISEG_CONV_HWC64=0 (read per call; A/B timing): the 64-Cout layers on conv_hwr (variant 100) instead of conv_hwc 107
-static bool hwc64_mode() {
-  const char* e = getenv("HISEG_CONV_HWC64");
-  return !(e && atoi(e) == 0);
-}
-
-// HISEG_CONV_HWC_R3=0 (read per call; A/B timing): the 128-Cout layers on variant 104 (two halo buffers) instead of 108
-static bool hwc_r3_mode() {
-  const char* e = getenv("HISEG_CONV_HWC_R3");
-  return !(e && atoi(e) == 0);
-}
-
-// HISEG_CONV_HWC_MTW=0|1 (read per call; A/B timing): the multi-tile conv_hwc forms (109 for 128-multiple Cout, 102 for
-// the 64-Cout layers) instead of 108 / 107
-#ifndef HISEG_CONV_HWC_MT_DEFAULT
-#define HISEG_CONV_HWC_MT_DEFAULT(bco) false
-#endif
-static bool hwc_mt_mode(int bco) {
-  const char* e = getenv("HISEG_CONV_HWC_MTW");
-  if (e) return atoi(e) != 0;
-  return HISEG_CONV_HWC_MT_DEFAULT(bco);
-}
-
-static bool release_variant(int v) {
-  return v == -1 || v == 0 || (v >= 1 && v <= 8) || v == 50 || v == 51 || v == 52 || v == 54 || v == 58 ||
-         (v >= 60 && v <= 69) || v == 70 || v == 71 || v == 72 || v == 74 || v == 80 || v == 82 || v == 84 || v == 86 ||
-         v == 88 || v == 89 || v == 90 || (v >= 92 && v <= 101) || v == 103 || v == 102 || (v >= 104 && v <= 109);
-}
-
-// Workspace bytes the automatic choice uses for this layer (split-K generic kernel), 0 when it needs none.
-extern "C" long long hiseg_conv2d_workspace_bytes(const hiseg_conv2d_desc* d) {
-  if (d == nullptr || d->dtype != HISEG_BF16 || d->convT || d->N <= 0) return 0;
-  const long long M = (long long)d->N * d->Ho * d->Wo;
-  if (M >= (1ll << 31) || d->K_pad % 64) return 0;
-  ConvArgs a;
-  a.d = *d;
-  a.M = (int)M;
-  a.Cin = d->Ca + d->Cb;
-  a.nK = d->K_pad / 64;
-  a.Hs = d->H / (d->a_up > 0 ? d->a_up : 1);
-  a.Ws = d->W / (d->a_up > 0 ? d->a_up : 1);
-  if (conv_pw_applies(a)) return 0;
-  // an SE-gated 1x1 layer whose gate table exceeds the pointwise kernel's LDS runs in image ranges on that kernel
-  // (conv2d_impl), never on the split-K path
-  if (d->in_scale && d->KH == 1 && d->KW == 1 && conv_pw_gate_images(a) > 0) return 0;
-  return splitk_bytes(a, splitk_plan(a));
-}
-
-extern "C" int hiseg_conv2d_stats_tiles(const hiseg_conv2d_desc* d) {
-  if (d == nullptr || d->dtype != HISEG_BF16 || d->convT || d->N <= 0) return 0;
-  const long long M = (long long)d->N * d->Ho * d->Wo;
-  if (M >= (1ll << 31)) return 0;
-  ConvArgs a;
-  a.d = *d;
-  a.M = (int)M;
-  a.Cin = d->Ca + d->Cb;
-  a.nK = d->K_pad / 64;
-  a.Hs = d->H / (d->a_up > 0 ? d->a_up : 1);
-  a.Ws = d->W / (d->a_up > 0 ? d->a_up : 1);
-  return conv_hwc_stats_tiles(a);
-}
-
-// The fused operands of rounds 7 and 8 -- whether any is set, and in a combination some kernel has: px_scale alone
-// (the pointwise kernel); head2_out, with or without res_gate; a_gate alone (the 3x3 halo kernel).
-static bool has_fused_operands(const hiseg_conv2d_desc* d) {
-  return d->px_scale || d->head2_out || d->a_gate || d->res_gate;
-}
-static bool fused_operands_ok(const hiseg_conv2d_desc* d) {
-  if (!has_fused_operands(d)) return false;
-  if (d->px_scale) return !d->head2_out && !d->a_gate && !d->res_gate;
-  if (d->a_gate) return !d->head2_out && !d->res_gate;
-  return d->head2_out != nullptr;   // (res_gate rides with head2_out only)
-}
-
-extern "C" int hiseg_conv2d_fused_ok(const hiseg_conv2d_desc* d) {
-  if (d == nullptr || d->dtype != HISEG_BF16 || d->N <= 0 || !fused_operands_ok(d) || d->stats_partial ||
-      d->bnb_partial || d->a_up != 1 || d->K_pad % 64)
-    return 0;
-  const long long M = (long long)d->N * d->Ho * d->Wo;
-  if (M >= (1ll << 31)) return 0;
-  ConvArgs a;
-  a.d = *d;
-  a.M = (int)M;
-  a.Cin = d->Ca + d->Cb;
-  a.nK = d->K_pad / 64;
-  a.Hs = d->H;
-  a.Ws = d->W;
-  return d->px_scale ? (conv_pw_applies(a) ? 1 : 0) : (conv_hwc_fused_variant(a, hwc_r3_mode()) ? 1 : 0);
-}
-
-extern "C" int hiseg_conv2d_fwd_variant(const hiseg_conv2d_desc* d, int variant, hiseg_stream_t stream) {
-#ifndef HISEG_DIAG
-  HISEG_REQUIRE(release_variant(variant), HISEG_ERR_BAD_ARG,
-                "conv2d: variant %d is not a release variant (diagnostic kernels need a DIAG=1 build)", variant);
-#endif
-  return conv2d_impl(d, stream, variant);
-}
-
-// the generic kernel, noted as generic / generic split-K with the Cout tile it launched
-template <typename T, typename TO>
-static int launch_generic(const ConvArgs& a, hipStream_t s, int splits = 1) {
-  const int r = launch_typed<T, TO>(a, s, splits);
-  if (r == HISEG_OK) conv_note_path(splits > 1 ? HISEG_CONV_PATH_GENERIC_SPLITK : HISEG_CONV_PATH_GENERIC, g_generic_bco);
-  return r;
-}
-
-extern "C" int hiseg_conv2d_last_path(void) { return g_conv_last; }
-
-extern "C" int hiseg_conv2d_path_stats(long long* counts, int n, int reset) {
-  for (int i = 0; i < HISEG_CONV_PATH_FAMILIES; ++i) {
-    // (reset: one exchange, so a launch counted on another thread between a load and a store is not lost)
-    const long long c = reset ? g_conv_paths[i].exchange(0) : g_conv_paths[i].load();
-    if (counts && i < n) counts[i] = c;
-  }
-  return HISEG_CONV_PATH_FAMILIES;
-}
-
-static int conv2d_impl(const hiseg_conv2d_desc* d, hiseg_stream_t stream, int variant) {
-  HISEG_REQUIRE(d != nullptr, HISEG_ERR_BAD_ARG, "conv2d: null descriptor");
-  HISEG_REQUIRE(d->dtype == HISEG_F32 || d->dtype == HISEG_BF16, HISEG_ERR_BAD_DTYPE, "conv2d: dtype %d", d->dtype);
-  HISEG_REQUIRE(d->out_dtype == HISEG_F32 || d->out_dtype == HISEG_BF16, HISEG_ERR_BAD_DTYPE, "conv2d: out_dtype %d", d->out_dtype);
-  HISEG_REQUIRE(d->srcA && d->weight && d->scale && d->shift && (d->out || d->head2_out), HISEG_ERR_BAD_ARG,
-                "conv2d: null pointer");
-#ifdef HISEG_DIAG
-  const bool fused_variant = variant == 0 || (variant == 148 && d->a_gate);   // (148: the gated form, for timing)
-#else
-  const bool fused_variant = variant == 0;
-#endif
-  HISEG_REQUIRE(!has_fused_operands(d) ||
-                    (fused_variant && !d->stats_partial && !d->bnb_partial && fused_operands_ok(d)),
-                HISEG_ERR_BAD_ARG,
-                "conv2d: px_scale / head2_out / a_gate / res_gate go with the automatic choice alone: px_scale or "
-                "a_gate by itself, res_gate only beside head2_out");
-  HISEG_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ho > 0 && d->Wo > 0, HISEG_ERR_BAD_SHAPE, "conv2d: empty grid");
-  HISEG_REQUIRE(d->KH > 0 && d->KW > 0 && d->stride > 0 && d->pad >= 0, HISEG_ERR_BAD_SHAPE, "conv2d: bad window");
-  HISEG_REQUIRE(d->a_up == 1 || d->a_up == 2, HISEG_ERR_BAD_SHAPE, "conv2d: a_up must be 1 or 2");
-  HISEG_REQUIRE(d->a_up == 1 || (d->H % 2 == 0 && d->W % 2 == 0), HISEG_ERR_BAD_SHAPE, "conv2d: upsampled grid must be even");
-  HISEG_REQUIRE(d->Cb == 0 || d->srcB, HISEG_ERR_BAD_ARG, "conv2d: Cb > 0 needs srcB");
-  HISEG_REQUIRE(d->Cout > 0 && d->Cout_pad >= d->Cout && d->Cout_pad % 16 == 0, HISEG_ERR_BAD_SHAPE,
-                "conv2d: Cout %d Cout_pad %d (must be multiple of 16)", d->Cout, d->Cout_pad);
-  const int kch = d->dtype == HISEG_BF16 ? 8 : 4;
-  const int bk = 8 * kch;
-  const int Cin = d->Ca + d->Cb;
-  HISEG_REQUIRE(d->Ca > 0 && d->Ca % kch == 0 && d->Cb % kch == 0 && d->a_cstride % kch == 0 &&
-                    d->a_coff % kch == 0 && (d->Cb == 0 || (d->b_cstride % kch == 0 && d->b_coff % kch == 0)),
-                HISEG_ERR_BAD_SHAPE, "conv2d: input channels/strides must be multiples of %d", kch);
-  HISEG_REQUIRE(d->K_pad % bk == 0 && d->K_pad >= d->KH * d->KW * Cin, HISEG_ERR_BAD_SHAPE,
-                "conv2d: K_pad %d must be a multiple of %d and >= %d", d->K_pad, bk, d->KH * d->KW * Cin);
-  HISEG_REQUIRE(al16(d->srcA) && al16(d->srcB) && al16(d->weight), HISEG_ERR_BAD_SHAPE, "conv2d: operands must be 16-B aligned");
-  HISEG_REQUIRE(!d->convT || (d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->Cout % 16 == 0 &&
-                              d->Ho == d->H && d->Wo == d->W),
-                HISEG_ERR_BAD_SHAPE, "conv2d: convT requires a 1x1 GEMM with Cout = 4*C, C %% 4 == 0");
-  // BatchNorm statistics fused into the epilogue: only the halo kernel's fused-statistics form computes them, and no
-  // fallback may silently skip them (the caller would finalize garbage)
-  if (d->stats_partial || d->bnb_partial) {   // (also the fused BatchNorm-backward reduction of a data gradient)
-    HISEG_REQUIRE(variant == 0 || variant == 104 || variant == 107, HISEG_ERR_BAD_ARG,
-                  "conv2d: stats_partial / bnb_partial with variant %d", variant);
-    HISEG_REQUIRE(al16(d->out) && al16(d->scale) && al16(d->shift), HISEG_ERR_BAD_SHAPE, "conv2d: alignment");
-    ConvArgs a;
-    a.d = *d;
-    a.M = (int)((long long)d->N * d->Ho * d->Wo);
-    a.Cin = Cin;
-    a.nK = d->K_pad / bk;
-    a.Hs = d->H / d->a_up;
-    a.Ws = d->W / d->a_up;
-    HISEG_REQUIRE(conv_hwc_stats_tiles(a) > 0, HISEG_ERR_BAD_ARG,
-                  "conv2d: stats_partial / bnb_partial set but the layer has no fused kernel (hiseg_conv2d_stats_tiles)");
-    const int sv = d->Cout % 128 == 0 ? 104 : 107;
-    const int r = conv_took(HISEG_CONV_PATH_HWC, sv, conv_hwc_try(a, (hipStream_t)stream, sv));
-    HISEG_REQUIRE(r != 0, HISEG_ERR_BAD_ARG, "conv2d: the fused-statistics kernel declined the layer");
-    return r < 0 ? r : HISEG_OK;
-  }
-  // Operands of >= 2 GiB: the LDS-DMA kernels address through 32-bit buffer offsets, so the launch is split
-  // into image ranges whose every operand spans < 2 GiB (NHWC images are contiguous blocks; the conv never
-  // mixes images), each range a launch of its own on the same stream.
-  {
-    const long long ea = d->dtype == HISEG_BF16 ? 2 : 4, eo = d->out_dtype == HISEG_BF16 ? 2 : 4;
-    const long long in_px = (long long)(d->H / d->a_up) * (d->W / d->a_up);
-    const long long out_px = (long long)d->Ho * d->Wo * (d->convT ? 4 : 1);
-    long long per = in_px * d->a_cstride * ea;
-    auto upd = [&](long long v) { if (v > per) per = v; };
-    if (d->srcB) upd((long long)d->H * d->W * d->b_cstride * ea);
-    if (d->residual) upd(out_px * d->r_cstride * ea);
-    if (d->mul) upd(out_px * d->m_cstride * ea);
-    upd(out_px * d->o_cstride * eo);
-    if (d->out2) upd(out_px * d->o2_cstride * ea);
-    const long long lim = (1ll << 31) - (1ll << 20);
-    int step = 0;
-    if (per * d->N > lim) {
-      HISEG_REQUIRE(per <= lim, HISEG_ERR_BAD_SHAPE, "conv2d: one image's operand exceeds 2 GiB");
-      step = (int)(lim / per);
-    }
-    if (variant == 0 && d->in_scale && d->dtype == HISEG_BF16 && d->KH == 1 && d->KW == 1) {
-      // an SE-gated 1x1 layer the pointwise kernel takes at up to `g` images per launch (its LDS gate table):
-      // image ranges of g, whatever the batch (batch-invariant numerics, conv_pw_gate_images)
-      ConvArgs ga;
-      ga.d = *d;
-      ga.M = (int)((long long)d->N * d->Ho * d->Wo < (1ll << 31) ? (long long)d->N * d->Ho * d->Wo : 0);
-      ga.Cin = d->Ca + d->Cb;
-      ga.nK = d->K_pad / (8 * kch);
-      ga.Hs = d->H / d->a_up;
-      ga.Ws = d->W / d->a_up;
-      const int g = conv_pw_gate_images(ga);
-      if (g > 0 && (step == 0 || g < step)) step = g;
-    }
-    if (step > 0 && step < d->N) {
-      for (int n0 = 0; n0 < d->N; n0 += step) {
-        hiseg_conv2d_desc c = *d;
-        c.N = d->N - n0 < step ? d->N - n0 : step;
-        auto at = [&](const void* p, long long bytes_per_image) {
-          return p ? (const void*)((const char*)p + bytes_per_image * n0) : p;
-        };
-        c.srcA = at(d->srcA, in_px * d->a_cstride * ea);
-        c.srcB = at(d->srcB, (long long)d->H * d->W * d->b_cstride * ea);
-        c.residual = at(d->residual, out_px * d->r_cstride * ea);
-        c.mul = at(d->mul, out_px * d->m_cstride * ea);
-        c.out = const_cast<void*>(at(d->out, out_px * d->o_cstride * eo));
-        c.out2 = const_cast<void*>(at(d->out2, out_px * d->o2_cstride * ea));
-        if (d->in_scale) c.in_scale = d->in_scale + (long long)n0 * d->Ca;   // per-image SE gate [N][Ca]
-        if (d->px_scale) c.px_scale = d->px_scale + n0 * in_px;              // per-pixel scale of source A
-        if (d->head2_out) c.head2_out = d->head2_out + 2 * n0 * out_px;      // [pixels][2]
-        if (d->a_gate) c.a_gate = d->a_gate + (long long)n0 * d->Ca;         // per-image channel gates [N][Ca]
-        if (d->res_gate) c.res_gate = d->res_gate + (long long)n0 * d->Cout;   // [N][Cout]
-        const int r = conv2d_impl(&c, stream, variant);
-        if (r) return r;
-      }
-      return HISEG_OK;
-    }
-  }
-  const long long M = (long long)d->N * d->Ho * d->Wo;
-  HISEG_REQUIRE(M < (1ll << 31), HISEG_ERR_BAD_SHAPE, "conv2d: too many pixels");
-  ConvArgs a;
-  a.d = *d;
-  a.M = (int)M;
-  a.Cin = Cin;
-  a.nK = d->K_pad / bk;
-  a.Hs = d->H / d->a_up;
-  a.Ws = d->W / d->a_up;
-  hipStream_t s = (hipStream_t)stream;
-  // Automatic choice (variant 0) = the fastest measured configuration per layer class
-  // (tools/conv_bench.py): LDS-DMA ring kernel, 128x128 tiles for Cout >= 128, 64x128 for 64.
-  a.ins_vec = d->in_scale != nullptr && ((uintptr_t)d->in_scale & 15) == 0 && (d->Ca & 3) == 0;
-  a.ws = static_cast<float*>(d->workspace);
-  a.kper = a.nK;
-  // The fused operands of round 7 exist in one kernel each, and no other kernel may take the layer and silently
-  // ignore them: the caller asks hiseg_conv2d_fused_ok first.
-  if (has_fused_operands(d)) {
-    const int fv = variant ? variant : hwc_r3_mode() ? 108 : 104;
-    const int r = d->px_scale ? conv_took(HISEG_CONV_PATH_PW, 90, conv_pw_try(a, s, 90))
-                              : conv_took(HISEG_CONV_PATH_HWC, fv, conv_hwc_try(a, s, fv));
-    HISEG_REQUIRE(r != 0, HISEG_ERR_BAD_ARG,
-                  "conv2d: no kernel takes this layer with px_scale / head2_out / a_gate / res_gate "
-                  "(hiseg_conv2d_fused_ok)");
-    return r < 0 ? r : HISEG_OK;
-  }
-  if (variant == 99 || variant == 0) {
-    // split-K generic kernel for small-grid, long-K 1x1 layers (variant 99 forces it when the plan splits)
-    const int sp = splitk_plan(a);
-    if (sp > 1 && d->workspace != nullptr && d->workspace_bytes >= splitk_bytes(a, sp) &&
-        !(variant == 0 && conv_pw_applies(a))) {
-      a.kper = (a.nK + sp - 1) / sp;
-      const int spl = (a.nK + a.kper - 1) / a.kper;
-      return d->out_dtype == HISEG_BF16 ? launch_generic<bf16_t, bf16_t>(a, s, spl) : launch_generic<bf16_t, float>(a, s, spl);
-    }
-    HISEG_REQUIRE(variant == 0, HISEG_ERR_BAD_ARG, "conv2d: variant 99 (split-K) does not apply to this layer / workspace");
-  }
-  if (variant == 98) {
-    const int r = conv_took(HISEG_CONV_PATH_ROWS, variant, conv_rows_try(a, s, variant));
-    if (r != 0) return r < 0 ? r : HISEG_OK;
-  } else if (variant == 90 || (variant >= 190 && variant < 222)) {
-    const int r = conv_took(HISEG_CONV_PATH_PW, variant, conv_pw_try(a, s, variant));
-    if (r != 0) return r < 0 ? r : HISEG_OK;
-  } else if ((variant >= 92 && variant <= 97) || variant == 100 || variant == 101 || (variant >= 110 && variant < 142)) {
-    const int r = conv_took(HISEG_CONV_PATH_HWR, variant, conv_hwr_try(a, s, variant));
-    if (r != 0) return r < 0 ? r : HISEG_OK;
-  } else if (variant == 102 || (variant >= 104 && variant <= 109) || (variant >= 150 && variant < 4300)) {
-    const int r = conv_took(HISEG_CONV_PATH_HWC, variant, conv_hwc_try(a, s, variant));
-    if (r != 0) return r < 0 ? r : HISEG_OK;
-  } else if (variant == 103) {
-    const int r = conv_took(HISEG_CONV_PATH_HWT, variant, conv_hwt_try(a, s, variant));
-    if (r != 0) return r < 0 ? r : HISEG_OK;
-  } else if (variant >= 80 && variant < 90) {
-    const int r = conv_took(HISEG_CONV_PATH_HW, variant, conv_hw_try(a, s, variant));
-    if (r != 0) return r < 0 ? r : HISEG_OK;
-  } else if (variant >= 70 && variant < 80) {
-    const int r = conv_took(HISEG_CONV_PATH_WIDE, variant, conv_wide_try(a, s, variant));
-    if (r != 0) return r < 0 ? r : HISEG_OK;
-  } else if (variant >= 60 && variant < 70) {
-    const int r = conv_took(HISEG_CONV_PATH_FAST, variant, conv_fast_try(a, s, variant));
-    if (r != 0) return r < 0 ? r : HISEG_OK;
-  } else if (variant >= 50) {
-    const int r = conv_took(HISEG_CONV_PATH_SMALL, variant, conv_small_try(a, s, variant));
-    if (r != 0) return r < 0 ? r : HISEG_OK;
-  } else if (variant >= 0) {
-    int v = variant;
-    // 61 = 128x128 ring, 8 waves as 4 (Cout) x 2 (pixel) with 32x64 wave tiles, LDS full-row epilogue;
-    // 68 = the same wave grid on 64x128 tiles (tools/conv_bench.py: +1..4 % / +7..9 % over the 4-wave
-    // 66 / 67, which had beaten the register epilogue by 4..17 %; all bit-identical)
-    // HISEG_CONV_WAVES=4 restores the 4-wave tiles (A/B timing only)
-    static const bool four_waves = [] { const char* e = getenv("HISEG_CONV_WAVES"); return e && atoi(e) == 4; }();
-    // 256-output-channel 3x3 layers: the wide-tile kernel (conv_wide.hip: 256x256 workgroup tile, 128x128 wave
-    // tiles, LDS epilogue; tools/conv_bench.py: 0.99 vs 1.23 ms on the 256->256 3x3 @64x48 x256 ROI class,
-    // 0.58 vs 0.66 ms on 128->256, bit-identical).  It declines what it does not cover.
-    // 3x3 single-source layers with 128-multiple Cout: the halo-tiled kernel, BCO 128 with B-fragment reuse
-    // across ky (conv_hw.hip, variant 86: two workgroups per CU; tools/conv_bench.py: 0.85 vs 1.02 ms (wide
-    // kernel) on the 256->256 @64x48 x256 ROI class, 1.01 vs 1.37 ms on 128->128 @128x96, 0.44 vs 0.54 ms on
-    // 128->256; channel-major K order, within bf16 rounding); 64-multiple Cout: its BCO-64 configuration (variant
-    // 89: 0.104 vs 0.140 ms on the 64->64 residual class, 0.26 vs 0.43 ms on 256->64)
-    // HISEG_CONV_HALO=0 keeps the tap-major kernels (A/B timing only)
-    static const bool halo = [] { const char* e = getenv("HISEG_CONV_HALO"); return !(e && atoi(e) == 0); }();
-    // 1x1 layers and the ConvTranspose GEMM with 256-multiple GEMM columns: the persistent pointwise kernel
-    // (conv_pw.hip, variant 90: weights resident in LDS, activations streamed into MFMA registers;
-    // tools/conv_bench.py: 0.205 vs 0.308 ms on 256->256 @64x48 x256 ROIs, 0.21 vs 0.34 ms on the 256+8
-    // combiner, 0.16 vs 0.24 ms on 128->256; bit-identical)
-    if (v == 0 && d->KH == 1 && d->KW == 1) {
-      const int r = conv_took(HISEG_CONV_PATH_PW, 90, conv_pw_try(a, s, 90));
-      if (r != 0) return r < 0 ? r : HISEG_OK;
-    }
-    // narrow 3x3 layers (16 / 32 output channels: the full-image UNet's last decoder blocks and head): the
-    // row-streaming kernel (conv_rows.hip, variant 98: weights in registers, input rows streamed through an LDS
-    // ring; bit-identical to conv_small)
-    if (v == 0 && d->KH == 3 && d->KW == 3 && d->Cout_pad <= 32) {
-      const int r = conv_took(HISEG_CONV_PATH_ROWS, 98, conv_rows_try(a, s, 98));
-      if (r != 0) return r < 0 ? r : HISEG_OK;
-      // (sources far apart in memory: conv_rows takes them through one buffer resource each, VERDICT r3 weak #1.)
-      // A layer of its form it still declines (an output alignment it does not store) takes conv_small, whose
-      // accumulation order is conv_rows' (bit-identical)
-      if (conv_rows_form(a)) {
-        const int r2 = conv_took(HISEG_CONV_PATH_SMALL, 0, conv_small_try(a, s, 0));
-        if (r2 != 0) return r2 < 0 ? r2 : HISEG_OK;
-      }
-    }
-    // 3x3 layers with weights also packed in MFMA fragment order (hiseg.ops.frag_pack) and 128-multiple Cout: the
-    // register-streamed-weight halo kernel (conv_hwr.hip: one barrier per 32-channel slice) in its B-reuse,
-    // MFMA-priority configuration (variant 97; tools/conv_bench.py, profiles/r3_conv_bench_hwr*.json: 0.732 vs
-    // 0.793 ms (variant 86) on 256->256 @64x48 x256 ROIs, 0.879 vs 0.930 ms on 128->128 @128x96, 0.364 vs 0.408 ms
-    // on 128->256; bit-identical to variant 86)
-    // Round 5: the Cout-split form of the same kernel (conv_hwc.hip, variant 104: each wave 32 Cout x all 256 pixels
-    // of the tile -- half the weight-fragment loads, each halo row's B fragment reused across the 3 ky taps;
-    // tools/conv_bench.py, profiles/r5_conv_hwc.txt: 256->256 @64x48 x256 ROIs 0.736 -> 0.678 ms, 128->128 @128x96
-    // 0.875 -> 0.799, 128->256 0.369 -> 0.345; bit-identical to variant 97 / 86)
-    // Round 6: variant 108, the same kernel with a ring of three halo buffers (slice sl + 2's halo in flight during
-    // slice sl; 72 KiB of LDS, two workgroups per CU): bit-identical, 256->256 @64x48 x256 ROIs 0.709 -> 0.701 ms,
-    // 128->128 @128x96 0.829 -> 0.814, 128->256 0.364 -> 0.351 (tools/conv_bench.py, profiles/r6_conv_hwc_r3.txt)
-    // Round 6: variants 109 / 102, multi-tile workgroups (conv_hwc_mt_kernel: the next tile's first halo slice lands
-    // during the last slice, two-half epilogue; bit-identical; HISEG_CONV_HWC_MTW=0|1 overrides the default)
-    if (v == 0 && !four_waves && halo && d->weight_frag != nullptr && d->Cout % 128 == 0 && hwc_mt_mode(128)) {
-      const int r = conv_took(HISEG_CONV_PATH_HWC, 109, conv_hwc_try(a, s, 109));
-      if (r != 0) return r < 0 ? r : HISEG_OK;
-    }
-    if (v == 0 && !four_waves && halo && d->weight_frag != nullptr && d->Cout % 128 == 0) {
-      const int cv = hwc_r3_mode() ? 108 : 104;
-      const int r = conv_took(HISEG_CONV_PATH_HWC, cv, conv_hwc_try(a, s, cv));
-      if (r != 0) return r < 0 ? r : HISEG_OK;
-    }
-    if (v == 0 && !four_waves && halo && d->weight_frag != nullptr && d->Cout % 128 == 0) {
-      const int r = conv_took(HISEG_CONV_PATH_HWR, 97, conv_hwr_try(a, s, 97));
-      if (r != 0) return r < 0 ? r : HISEG_OK;
-    }
-    // 64-multiple Cout (the EnhancedUNet's 64-channel layers, the smp decoder's 64-channel block): conv_hwc on 64-Cout
-    // x 16 x 32-pixel tiles (variant 107, round 5), else conv_hwr's (variant 100)
-    if (v == 0 && !four_waves && halo && d->weight_frag != nullptr && d->Cout % 64 == 0 && hwc64_mode() &&
-        hwc_mt_mode(64)) {
-      const int r = conv_took(HISEG_CONV_PATH_HWC, 102, conv_hwc_try(a, s, 102));
-      if (r != 0) return r < 0 ? r : HISEG_OK;
-    }
-    if (v == 0 && !four_waves && halo && d->weight_frag != nullptr && d->Cout % 64 == 0 && hwc64_mode()) {
-      const int r = conv_took(HISEG_CONV_PATH_HWC, 107, conv_hwc_try(a, s, 107));
-      if (r != 0) return r < 0 ? r : HISEG_OK;
-    }
-    if (v == 0 && !four_waves && halo && d->weight_frag != nullptr && d->Cout % 64 == 0) {
-      const int r = conv_took(HISEG_CONV_PATH_HWR, 100, conv_hwr_try(a, s, 100));
-      if (r != 0) return r < 0 ? r : HISEG_OK;
-    }
-    if (v == 0 && !four_waves && halo) {
-      // (BCO 64 for every Cout that is not a 128 multiple: full 64 tiles plus a partial last tile)
-      const int hv = d->Cout % 128 ? 89 : 86;
-      const int r = conv_took(HISEG_CONV_PATH_HW, hv, conv_hw_try(a, s, hv));
-      if (r != 0) return r < 0 ? r : HISEG_OK;
-    }
-    if (v == 0 && d->Cout % 256 == 0 && d->KH * d->KW > 1 && !four_waves) {
-      const int r = conv_took(HISEG_CONV_PATH_WIDE, 70, conv_wide_try(a, s, 70));
-      if (r != 0) return r < 0 ? r : HISEG_OK;
-    }
-    if (v == 0) v = four_waves ? ((d->Cout_pad % 128 == 0) ? 66 : 67) : ((d->Cout_pad % 128 == 0) ? 61 : 68);
-    const int r = conv_took(HISEG_CONV_PATH_FAST, v, conv_fast_try(a, s, v));
-    if (r != 0) return r < 0 ? r : HISEG_OK;
-    if (variant == 0) {   // narrow / ragged layers: halo-tiled direct kernel
-      const int r2 = conv_took(HISEG_CONV_PATH_SMALL, 0, conv_small_try(a, s, 0));
-      if (r2 != 0) return r2 < 0 ? r2 : HISEG_OK;
-    }
-  }
-  if (d->dtype == HISEG_BF16) {
-    return d->out_dtype == HISEG_BF16 ? launch_generic<bf16_t, bf16_t>(a, s) : launch_generic<bf16_t, float>(a, s);
-  }
-  return d->out_dtype == HISEG_BF16 ? launch_generic<float, bf16_t>(a, s) : launch_generic<float, float>(a, s);
-}

@@ -344,39 +344,11 @@ def conv2d(p: ConvPlan, xa: Act, xb: Optional[Act] = None, out: Optional[Act] = 
                       zero=None if out_cpad is None else out_cpad != p.cout)
     assert out is None or (out.N, out.H, out.W) == (xa.N, oH, oW), ((out.N, out.H, out.W), (xa.N, oH, oW))
     assert xa.C <= p.ca and (xb is None or xb.C <= p.cb)
-    d = L.Conv2dDesc()
-    d.dtype, d.out_dtype = hdtype(dt), hdtype(out.dtype if out is not None else (out_dtype or dt))
-    d.N, d.H, d.W, d.Ho, d.Wo = xa.N, H, W, Ho, Wo
-    d.KH, d.KW, d.stride, d.pad = p.kh, p.kw, p.stride, p.pad
-    d.srcA, d.a_cstride, d.a_coff, d.Ca, d.a_up = xa, xa.cstride, xa.coff, p.ca, a_up
-    if xb is not None:
-        d.srcB, d.b_cstride, d.b_coff, d.Cb = xb, xb.cstride, xb.coff, p.cb
-    if in_scale is not None:
-        d.in_scale = in_scale
-    d.weight, d.Cout, d.Cout_pad, d.K_pad = p.weight, p.gemm_cols, p.cout_pad, p.k_pad
-    d.scale, d.shift, d.act, d.act_beta = p.scale, p.shift, int(p.act), L.act_beta(p.act)
-    if residual is not None:
-        d.residual, d.r_cstride, d.r_coff = residual, residual.cstride, residual.coff
-    if mul is not None:
-        d.mul, d.m_cstride, d.m_coff = mul, mul.cstride, mul.coff
-    if out is not None:
-        d.out, d.o_cstride, d.o_coff = out, out.cstride, out.coff
-    else:   # (head2 in the epilogue: the output tile is not stored)
-        d.o_cstride, d.o_coff = p.cout, 0
+    if out is None:   # (head2 in the epilogue: the output tile is not stored)
         head2.out = torch.empty(xa.N * oH * oW, 2, dtype=torch.float32, device=xa.t.device)
-        d.head2_w, d.head2_b, d.head2_out = head2.w, head2.b, head2.out
-    if fused and px_scale is not None:
-        d.px_scale = px_scale
-    if a_gate is not None:
-        d.a_gate = a_gate
-    if res_gate is not None:
-        d.res_gate = res_gate
-    if out2 is not None:
-        assert out2.dtype == dt
-        d.out2, d.o2_cstride, d.o2_coff = out2, out2.cstride, out2.coff
-    d.convT = int(p.convT)
-    if p.weight_frag is not None:
-        d.weight_frag = p.weight_frag
+    d = _conv_desc(p, xa, xb, residual, mul, out, a_up=a_up, in_scale=in_scale, out_dtype=out_dtype, out2=out2,
+                   px_scale=px_scale if fused else None, head2=head2 if out is None else None,
+                   head2_out=head2.out if out is None else None, a_gate=a_gate, res_gate=res_gate)
     ws = None
     if dt == torch.bfloat16 and not p.convT and ((p.kh * p.kw == 1 and p.k_pad >= 384) or
                                                  (split_k_3x3 and p.kh * p.kw == 9)):
@@ -391,12 +363,10 @@ def conv2d(p: ConvPlan, xa: Act, xb: Optional[Act] = None, out: Optional[Act] = 
     if RECORD is not None:
         dc = d.copy()
         keep = [t for t in (xa, xb, out, residual, mul, out2, ws, px_scale, a_gate, res_gate) if t is not None]
-        flops = 2.0 * d.N * d.Ho * d.Wo * p.gemm_cols * p.kh * p.kw * (xa.C + (xb.C if xb is not None else 0))
-        RECORD.append((dc, keep, p, flops))
+        RECORD.append((dc, keep, p, _conv_flops(d, p, xa, xb)))
     gate = GATE
     if gate is not None:
-        flops = 2.0 * d.N * d.Ho * d.Wo * p.gemm_cols * p.kh * p.kw * (xa.C + (xb.C if xb is not None else 0))
-        if flops >= gate.min_flops and not variant:
+        if _conv_flops(d, p, xa, xb) >= gate.min_flops and not variant:
             gate.before()
             _launch_conv(d, p, xa, xb)
             gate.after()
@@ -404,6 +374,59 @@ def conv2d(p: ConvPlan, xa: Act, xb: Optional[Act] = None, out: Optional[Act] = 
         gate.light()
     _launch_conv(d, p, xa, xb, variant)
     return out
+
+
+def _conv_desc(p, xa, xb, residual, mul, out, *, a_up=1, in_scale=None, out_dtype=None, out2=None, px_scale=None,
+               head2=None, head2_out=None, a_gate=None, res_gate=None):
+    """The Conv2dDesc of one layer, for a launch (conv2d) or a plan (_fused_ok).  ``out`` None: no output tile is
+    described beyond a dense [.., Cout] view of ``out_dtype`` -- head2 stores ``head2_out`` instead, and a plan has
+    no output yet."""
+    dt = xa.dtype
+    H, W = xa.H * a_up, xa.W * a_up
+    d = L.Conv2dDesc()
+    d.dtype, d.out_dtype = hdtype(dt), hdtype(out.dtype if out is not None else (out_dtype or dt))
+    d.N, d.H, d.W = xa.N, H, W
+    if p.convT:
+        d.Ho, d.Wo = H, W
+    else:
+        d.Ho = (H + 2 * p.pad - p.kh) // p.stride + 1
+        d.Wo = (W + 2 * p.pad - p.kw) // p.stride + 1
+    d.KH, d.KW, d.stride, d.pad = p.kh, p.kw, p.stride, p.pad
+    d.srcA, d.a_cstride, d.a_coff, d.Ca, d.a_up = xa, xa.cstride, xa.coff, p.ca, a_up
+    if xb is not None:
+        d.srcB, d.b_cstride, d.b_coff, d.Cb = xb, xb.cstride, xb.coff, p.cb
+    if in_scale is not None:
+        d.in_scale = in_scale
+    d.weight, d.Cout, d.Cout_pad, d.K_pad = p.weight, p.gemm_cols, p.cout_pad, p.k_pad
+    d.scale, d.shift, d.act, d.act_beta = p.scale, p.shift, int(p.act), L.act_beta(p.act)
+    if residual is not None:
+        d.residual, d.r_cstride, d.r_coff = residual, residual.cstride, residual.coff
+    if mul is not None:
+        d.mul, d.m_cstride, d.m_coff = mul, mul.cstride, mul.coff
+    if out is not None:
+        d.out, d.o_cstride, d.o_coff = out, out.cstride, out.coff
+    else:
+        d.o_cstride, d.o_coff = p.cout, 0
+    if head2 is not None:
+        d.head2_w, d.head2_b, d.head2_out = head2.w, head2.b, head2_out
+    if px_scale is not None:
+        d.px_scale = px_scale
+    if a_gate is not None:
+        d.a_gate = a_gate
+    if res_gate is not None:
+        d.res_gate = res_gate
+    if out2 is not None:
+        assert out2.dtype == dt
+        d.out2, d.o2_cstride, d.o2_coff = out2, out2.cstride, out2.coff
+    d.convT = int(p.convT)
+    if p.weight_frag is not None:
+        d.weight_frag = p.weight_frag
+    return d
+
+
+def _conv_flops(d, p, xa, xb) -> float:
+    """Multiply-adds x 2 of one launch over the channels the sources really hold (RECORD, GATE and PROBE)."""
+    return 2.0 * d.N * d.Ho * d.Wo * p.gemm_cols * p.kh * p.kw * (xa.C + (xb.C if xb is not None else 0))
 
 
 def _fused_ok(p, xa, xb, residual, mul, in_scale, px_scale, head2, out_dtype, a_up, a_gate=None, res_gate=None) -> bool:
@@ -425,34 +448,11 @@ def _fused_ok(p, xa, xb, residual, mul, in_scale, px_scale, head2, out_dtype, a_
             return False
         assert head2.w.dtype == torch.float32 and head2.w.is_contiguous() and tuple(head2.w.shape) == (2, p.cout)
         assert head2.b.dtype == torch.float32 and head2.b.numel() == 2
-    d = L.Conv2dDesc()
-    d.dtype = d.out_dtype = L.HISEG_BF16
-    d.N, d.H, d.W = xa.N, xa.H, xa.W
-    if p.convT:
-        d.Ho, d.Wo = xa.H, xa.W
-    else:
-        d.Ho = (xa.H + 2 * p.pad - p.kh) // p.stride + 1
-        d.Wo = (xa.W + 2 * p.pad - p.kw) // p.stride + 1
-    d.KH, d.KW, d.stride, d.pad = p.kh, p.kw, p.stride, p.pad
-    d.srcA, d.a_cstride, d.a_coff, d.Ca, d.a_up = xa, xa.cstride, xa.coff, p.ca, 1
-    d.weight, d.Cout, d.Cout_pad, d.K_pad = p.weight, p.gemm_cols, p.cout_pad, p.k_pad
-    d.scale, d.shift, d.act, d.act_beta = p.scale, p.shift, int(p.act), L.act_beta(p.act)
-    d.o_cstride, d.o_coff = p.cout, 0
-    d.convT = int(p.convT)
-    if p.weight_frag is not None:
-        d.weight_frag = p.weight_frag
-    if residual is not None:
-        d.residual, d.r_cstride, d.r_coff = residual, residual.cstride, residual.coff
-    if px_scale is not None:
-        d.px_scale = px_scale
+    # (head2.w for head2_out: the plan looks at its alignment only, and nothing is launched)
+    d = _conv_desc(p, xa, None, residual, None, None, out_dtype=out_dtype, px_scale=px_scale, head2=head2,
+                   head2_out=head2.w if head2 is not None else None, a_gate=a_gate, res_gate=res_gate)
+    if px_scale is not None or a_gate is not None:
         d.out = xa   # (any aligned address: the plan looks at the output's alignment only)
-    if head2 is not None:
-        d.head2_w, d.head2_b, d.head2_out = head2.w, head2.b, head2.w
-    if a_gate is not None:
-        d.a_gate = a_gate
-        d.out = xa
-    if res_gate is not None:
-        d.res_gate = res_gate
     return bool(L.lib().hiseg_conv2d_fused_ok(ctypes.byref(d)))
 
 
@@ -460,8 +460,7 @@ def _launch_conv(d, p, xa, xb, variant=0):
     if PROBE is not None:
         key = PROBE.select(d)
         if key is not None:
-            flops = 2.0 * d.N * d.Ho * d.Wo * p.gemm_cols * p.kh * p.kw * (xa.C + (xb.C if xb is not None else 0))
-            L.check(PROBE.around(key, flops, lambda: L.lib().hiseg_conv2d_fwd(ctypes.byref(d), L.stream_ptr())),
+            L.check(PROBE.around(key, _conv_flops(d, p, xa, xb), lambda: L.lib().hiseg_conv2d_fwd(ctypes.byref(d), L.stream_ptr())),
                     "conv2d")
             return
     if variant:

@@ -473,9 +473,9 @@ def f32_rule(name, what, k, ref, r32):
     assert ratio <= 1.0, f"{name} {what}: error / bound = {ratio:.3f}"
 
 
-# conv_hwc's fused-statistics forms (train mode): conv2d_impl's first branch.  It picks the kernel by Cout alone --
-# `sv = d->Cout % 128 == 0 ? 104 : 107` -- whichever of 0 / 104 / 107 the caller passed; no activation, no residual;
-# the upsampled source with stats_partial only (`d.bnb_partial && (... || d.a_up != 1 ...)` in conv_hwc_applies).
+# conv_hwc's fused-statistics forms (train mode): conv2d_impl's first branch (csrc/conv_dispatch.cpp).  It picks the
+# kernel by Cout alone -- `d->Cout % 128 == 0 ? 104 : 107` -- whichever of 0 / 104 / 107 the caller passed; no
+# activation, no residual; the upsampled source with stats_partial only (`d.bnb_partial && (... || d.a_up != 1 ...)` in conv_hwc_applies).
 STATS = {
     "64to128_17x33": C(Ca=64, Cout=128, H=17, W=33),
     "128to256_two_cout_tiles_16x16": C(Ca=128, Cout=256, H=16, W=16),
@@ -626,7 +626,7 @@ def test_rows(name, variant):
 
 
 # ------------------------------------------------------------------------------------------- automatic choice
-# The path conv2d_impl's chain (csrc/conv_igemm.hip) names for each layer class, read from the code:
+# The path the candidate list of auto_candidates (csrc/conv_dispatch.cpp) gives each layer class, read from the code:
 AUTO = {
     "pw_1x1_256to256": (C(Ca=256, Cout=256, H=9, W=7, k=1, pad=0, act=1), ("pw", 90), "bf16"),
     "rows_3x3_16to16": (C(Ca=16, Cout=16, H=9, W=21, act=1), ("rows", 98), "bf16"),
@@ -651,6 +651,26 @@ AUTO = {
 def test_automatic_choice(name):
     case, path, dt = AUTO[name]
     check(case, 0, path, dt, tiers="A")
+
+
+# The toggles auto_candidates reads per call, on layers of the HALO table (test_halo forces the same variants on them):
+# (variable, value, HALO layer, Cout, path)
+AUTO_TOGGLES = [
+    ("HISEG_CONV_HWC_R3", "0", "17x33_past_both_tiles_128_res", 128, ("hwc", 104)),   # two halo buffers, not 108's ring
+    ("HISEG_CONV_HWC64", "0", "16x16_one_tile_64", 64, ("hwr", 100)),                 # conv_hwr, not conv_hwc 107
+    ("HISEG_CONV_HWC_MTW", "1", "17x33_past_both_tiles_128_res", 128, ("hwc", 109)),  # the multi-tile forms
+    ("HISEG_CONV_HWC_MTW", "1", "16x16_one_tile_64", 64, ("hwc", 102)),
+]
+
+
+@pytest.mark.parametrize("var,value,name,cout,path", AUTO_TOGGLES,
+                         ids=[f"{t[0]}={t[1]}_cout{t[3]}" for t in AUTO_TOGGLES])
+def test_automatic_choice_toggles(var, value, name, cout, path, monkeypatch):
+    """HISEG_CONV_HWC_R3 / HISEG_CONV_HWC64 / HISEG_CONV_HWC_MTW move the automatic choice of a 128- / 64-Cout
+    fragment layer to another bit-identical kernel (HISEG_CONV_HALO and HISEG_CONV_WAVES are read once per process
+    and cannot be set here)."""
+    monkeypatch.setenv(var, value)
+    check(dict(HALO[name], Cout=cout), 0, path, "bf16", tiers="A")
 
 
 # ------------------------------------------------------------------------------------------- declines

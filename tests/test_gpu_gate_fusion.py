@@ -5,7 +5,7 @@ channel_scale pass it replaces, bit for bit.
   the halo pieces through registers) == ops.channel_scale followed by the same conv.
 * ``conv2d(residual=x, res_gate=g, head2=...)``: the residual read as bf16(x * g[image][channel]) in the epilogue that
   also applies the trailing 1x1 (conv_hwc.hip H2 + RG) == the same conv on the channel_scale'd residual.
-* Batch chunking: a batch whose operands exceed 2 GiB is split into image ranges (conv_igemm.hip); the gate tables
+* Batch chunking: a batch whose operands exceed 2 GiB is split into image ranges (conv_dispatch.cpp); the gate tables
   must move with the images.
 * Fallback: f32 and a 64-channel layer have no such form; conv2d runs the channel_scale pass itself.
 * End to end: engine.hier_head on the golden B0 head (bf16) with the gate fused == the same head with the fusion

@@ -153,7 +153,7 @@ def test_conv_transpose_and_in_scale(dt):
 # Which kernel ran.  A forced variant whose kernel declines the layer falls through to the generic kernel, and a
 # comparison with the generic kernel then compares it with itself: after every forced call the tests below read the
 # path the library recorded (hiseg._lib.conv_last_path) and require the family the variant belongs to in
-# conv2d_impl's chain (csrc/conv_igemm.hip) -- or, for a pair listed in a DECLINES set, the generic kernel.
+# the kFamilies table (csrc/conv_dispatch.cpp) -- or, for a pair listed in a DECLINES set, the generic kernel.
 def _family(v):
     if v == 98:
         return "rows"

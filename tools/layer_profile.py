@@ -22,10 +22,33 @@ from hiseg import _lib as L  # noqa: E402
 from hiseg import ops  # noqa: E402
 
 
+def layer_key(d):
+    return (f"k{d.KH}x{d.KW} s{d.stride} up{d.a_up} {d.Ca}+{d.Cb}->{d.Cout}(pad{d.Cout_pad}) "
+            f"{d.N}x{d.Ho}x{d.Wo}{' T' if d.convT else ''}{' res' if d.residual else ''}"
+            f"{' f32out' if d.out_dtype == 0 else ''}{' ins' if d.in_scale else ''}")
+
+
+def print_paths(rec):
+    """One replay of every recorded launch through hiseg_conv2d_fwd: per layer key, in recording order, the
+    (family, variant) the library reports for it (hiseg._lib.conv_last_path) and how many launches took it."""
+    paths = {}
+    for d, keep, p, flops in rec:
+        L.check(L.lib().hiseg_conv2d_fwd(ctypes.byref(d), L.stream_ptr()), "replay")
+        fam, v = L.conv_last_path()
+        took = paths.setdefault(layer_key(d), {})
+        took[(fam, v)] = took.get((fam, v), 0) + 1
+    torch.cuda.synchronize()
+    print(f"{len(rec)} conv launches")
+    for key, took in paths.items():
+        print("  ".join(f"{n}x {fam} {v}" for (fam, v), n in took.items()) + f"  {key}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--variant", type=int, default=0)
+    ap.add_argument("--paths", action="store_true",
+                    help="no timing: replay each launch once through hiseg_conv2d_fwd and print the kernel that took it")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     model = bench.build_model(dev, torch.bfloat16)
@@ -39,6 +62,9 @@ def main():
         wrap(images, rois)
         torch.cuda.synchronize()
     rec, ops.RECORD = ops.RECORD, None
+    if args.paths:
+        print_paths(rec)
+        return
     groups = {}
     total = 0.0
     for d, keep, p, flops in rec:
@@ -65,9 +91,7 @@ def main():
             byts += px_out * cout * esz
         if d.mul:
             byts += px_out * cout * esz
-        key = (f"k{d.KH}x{d.KW} s{d.stride} up{d.a_up} {d.Ca}+{d.Cb}->{d.Cout}(pad{d.Cout_pad}) "
-               f"{d.N}x{d.Ho}x{d.Wo}{' T' if d.convT else ''}{' res' if d.residual else ''}"
-               f"{' f32out' if d.out_dtype == 0 else ''}{' ins' if d.in_scale else ''}")
+        key = layer_key(d)
         g = groups.setdefault(key, {"n": 0, "ms": 0.0, "flops": flops, "bytes": byts})
         g["n"] += 1
         g["ms"] += ms
