@@ -491,7 +491,17 @@ __device__ __forceinline__ void bn_pre_tables(const hiseg_bn_bwd_desc& d, int c,
   }
 }
 
-// g = dy (* chan_mul) * act'(.) for one 16-B chunk; z = the chunk's pre-BN values (already loaded)
+// a * b rounded to f32: not a candidate for fusion into an add or subtract that consumes it
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// g = dy (* chan_mul) * act'(.) for one 16-B chunk; z = the chunk's pre-BN values (already loaded).  The products
+// are mul_rounded, so dz, dres and the sums are all built from one rounded g whatever code surrounds the call: the
+// U = 1 instance of bn_bwd_apply_vec_kernel used to fuse g's last multiply into g - sum(g)/P while the U = 2 instance,
+// with the multiply in its load loop (another basic block), could not, and their f32 dz were one rounding apart for
+// sigmoid / SiLU / GELU / Swish.
 template <typename T, int MODE>
 __device__ __forceinline__ void bn_gv(const hiseg_bn_bwd_desc& d, int p, int c, float* g, const float* z,
                                       const float* fs, const float* fh) {
@@ -500,7 +510,7 @@ __device__ __forceinline__ void bn_gv(const hiseg_bn_bwd_desc& d, int p, int c, 
   if (d.chan_mul) {
     const float* cm = d.chan_mul + (long long)(p / d.HW) * d.C + c;
 #pragma unroll
-    for (int k = 0; k < V; ++k) g[k] *= cm[k];
+    for (int k = 0; k < V; ++k) g[k] = mul_rounded(g[k], cm[k]);
   }
   if constexpr (MODE == kGReLU || MODE == kGPre) {
     float rr[V];
@@ -510,13 +520,13 @@ __device__ __forceinline__ void bn_gv(const hiseg_bn_bwd_desc& d, int p, int c, 
       float v = z[k] * fs[k] + fh[k];
       if (d.residual) v += rr[k];
       if constexpr (MODE == kGReLU) g[k] = v > 0.f ? g[k] : 0.f;
-      else g[k] *= act_grad_pre(v, d.act, d.act_beta);
+      else g[k] = mul_rounded(g[k], act_grad_pre(v, d.act, d.act_beta));
     }
   } else if constexpr (MODE == kGY) {
     float y[V];
     ldv<T>(d.y, (long long)p * d.y_cstride + d.y_coff + c, y);
 #pragma unroll
-    for (int k = 0; k < V; ++k) g[k] *= act_grad(y[k], d.act);
+    for (int k = 0; k < V; ++k) g[k] = mul_rounded(g[k], act_grad(y[k], d.act));
   }
 }
 
@@ -1181,9 +1191,15 @@ using namespace hiseg;
 
 extern "C" int hiseg_bn_partials(void) { return kBnSplits; }
 
-// pixels per iteration of the element-wise BN passes (HISEG_BN_U, read per call: A/B timing; same results).  Two
-// measured no faster (tools/bn_bench.py, profiles/r4_bn_bench.txt: apply 5.1-5.4 TB/s, backward 4.3-4.7 TB/s of
-// algorithmic bytes at U = 1 -- 0.7-0.85 of the ~6.3 TB/s a copy reaches), so U = 1 stays
+// Which kernels this thread's last BatchNorm entry point launched (hiseg_bn_last_path, HISEG_BN_PATH_* of
+// hiseg_train.h): a host integer written just before the launches; it chooses nothing.
+static thread_local int g_bn_last = -1;
+extern "C" int hiseg_bn_last_path(void) { return g_bn_last; }
+
+// pixels per iteration of the element-wise BN passes (HISEG_BN_U, read per call: A/B timing; the same bits,
+// tests/test_gpu_bn_kernels.py).  Two measured no faster (tools/bn_bench.py, profiles/r4_bn_bench.txt: apply
+// 5.1-5.4 TB/s, backward 4.3-4.7 TB/s of algorithmic bytes at U = 1 -- 0.7-0.85 of the ~6.3 TB/s a copy reaches),
+// so U = 1 stays
 static int bn_unroll() {
   const char* e = getenv("HISEG_BN_U");
   return e && atoi(e) == 2 ? 2 : 1;
@@ -1227,7 +1243,9 @@ static bool bn_fin_rows(int S) {
 static void bn_fin_launch(const float* partial, int S, int C, long long P, const float* gamma, const float* beta,
                           float eps, float momentum, float* rm, float* rv, float* mean, float* invstd, float* scale,
                           float* shift, hipStream_t stream, long long rs) {
-  if (bn_fin_rows(S))
+  const bool rows = bn_fin_rows(S);
+  g_bn_last = HISEG_BN_PATH_FINALIZE | (rows ? 0 : HISEG_BN_PATH_PAR);
+  if (rows)
     hipLaunchKernelGGL(bn_finalize_rows_kernel, dim3((unsigned)((C + 15) / 16)), dim3(256), 0, stream, partial, S, C,
                        P, gamma, beta, eps, momentum, rm, rv, mean, invstd, scale, shift, rs);
   else
@@ -1243,11 +1261,13 @@ extern "C" int hiseg_bn_stats(int dtype, const void* z, long long P, int C, int 
   if (vec_ok(dtype, C, z, cstride, coff)) {
     const int V = dtype == HISEG_BF16 ? 8 : 4;
     dim3 grid(S, (C / V + 255) / 256);
+    g_bn_last = HISEG_BN_PATH_STATS | HISEG_BN_PATH_VEC;
     DISPATCH_T(dtype, hipLaunchKernelGGL(bn_stats_vec_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, z, P, C,
                                          cstride, coff, partial));
     return hiseg_check_launch("bn_stats");
   }
   dim3 grid(S, (C + 255) / 256);
+  g_bn_last = HISEG_BN_PATH_STATS;
   DISPATCH_T(dtype, hipLaunchKernelGGL(bn_stats_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, z, P, C, cstride,
                                        coff, partial));
   return hiseg_check_launch("bn_stats");
@@ -1286,8 +1306,10 @@ extern "C" int hiseg_bn_finalize_n(float* partial, int S, int C, long long P, co
     S = G;
     rs *= KPRE;
   }
-  return bn_finalize_splits(partial, S, C, P, gamma, beta, eps, momentum, running_mean, running_var, mean, invstd,
-                            scale, shift, (hipStream_t)stream, rs);
+  const int e = bn_finalize_splits(partial, S, C, P, gamma, beta, eps, momentum, running_mean, running_var, mean,
+                                   invstd, scale, shift, (hipStream_t)stream, rs);
+  if (rs != 3ll * C) g_bn_last |= HISEG_BN_PATH_PREMERGE;
+  return e;
 }
 
 extern "C" int hiseg_bn_apply(const hiseg_bn_apply_desc* d, hiseg_stream_t stream) {
@@ -1296,6 +1318,7 @@ extern "C" int hiseg_bn_apply(const hiseg_bn_apply_desc* d, hiseg_stream_t strea
   HISEG_REQUIRE(d->P < (1ll << 31), HISEG_ERR_BAD_SHAPE, "bn_apply: too many pixels");
   if (vec_ok(d->dtype, d->C, d->z, d->z_cstride, d->z_coff) && vec_ok(d->dtype, d->C, d->y, d->y_cstride, d->y_coff) &&
       vec_ok(d->dtype, d->C, d->residual, d->r_cstride, d->r_coff)) {
+    g_bn_last = HISEG_BN_PATH_APPLY | HISEG_BN_PATH_VEC | (bn_unroll() == 2 ? HISEG_BN_PATH_U2 : 0);
     if (bn_unroll() == 2)
       DISPATCH_T(d->dtype, hipLaunchKernelGGL((bn_apply_vec_kernel<T, 2>), vec_grid(d->P, d->C, d->dtype), dim3(256),
                                               0, (hipStream_t)stream, *d));
@@ -1304,6 +1327,7 @@ extern "C" int hiseg_bn_apply(const hiseg_bn_apply_desc* d, hiseg_stream_t strea
                                               0, (hipStream_t)stream, *d));
     return hiseg_check_launch("bn_apply");
   }
+  g_bn_last = HISEG_BN_PATH_APPLY;
   DISPATCH_T(d->dtype, hipLaunchKernelGGL(bn_apply_kernel<T>, dim3(ew_blocks(d->P * d->C)), dim3(256), 0,
                                           (hipStream_t)stream, *d));
   return hiseg_check_launch("bn_apply");
@@ -1359,11 +1383,14 @@ extern "C" int hiseg_bn_bwd(const hiseg_bn_bwd_desc* d_in, hiseg_stream_t stream
   // the reduction already done by the data-gradient conv's epilogue (hiseg_conv2d_desc.bnb_partial): more than
   // 4 KPRE splits are summed in groups first, into the region after them
   const bool pre_red = d->partial_splits > 0;
+  int path = HISEG_BN_PATH_BWD | HISEG_BN_PATH_PAR | (bn_bwd_mode(*d) << HISEG_BN_PATH_MODE_SHIFT) |
+             (pre_red ? 0 : HISEG_BN_PATH_REDUCE);
   if (pre_red) {
     S = d->partial_splits;
     if (S > 4 * KPRE) {
       const int G = (S + KPRE - 1) / KPRE;
       float* grp = dd.partial + (long long)S * 3 * C;
+      g_bn_last = path |= HISEG_BN_PATH_PREMERGE;
       hipLaunchKernelGGL(bn_bwd_premerge_kernel, dim3((C + 63) / 64, G), dim3(256), 0, s, d->partial, S, C, grp);
       const int e = hiseg_check_launch("bn_bwd_premerge");
       if (e) return e;
@@ -1377,6 +1404,7 @@ extern "C" int hiseg_bn_bwd(const hiseg_bn_bwd_desc* d_in, hiseg_stream_t stream
     const int V = dt == HISEG_BF16 ? 8 : 4;
     const dim3 rgrid(S, (C / V + 255) / 256), agrid = vec_grid(d->P, C, dt);
     const int mode = bn_bwd_mode(*d);
+    g_bn_last = path | HISEG_BN_PATH_VEC | (bn_unroll() == 2 ? HISEG_BN_PATH_U2 : 0);
 #define BN_BWD_VEC(M)                                                                                         \
   do {                                                                                                        \
     if (!pre_red)                                                                                             \
@@ -1396,6 +1424,7 @@ extern "C" int hiseg_bn_bwd(const hiseg_bn_bwd_desc* d_in, hiseg_stream_t stream
 #undef BN_BWD_VEC
     return hiseg_check_launch("bn_bwd");
   }
+  g_bn_last = path;
   if (!pre_red)
     DISPATCH_T(d->dtype, hipLaunchKernelGGL(bn_bwd_reduce_kernel<T>, dim3(S, (d->C + 255) / 256), dim3(256), 0, s, *d));
   hipLaunchKernelGGL(bn_bwd_finalize_par_kernel, fin_grid(C), dim3(256), 0, s, *d, S);

@@ -336,6 +336,7 @@ def _declare(lib):
         "hiseg_conv2d_wgrad_reduce": ([P, c_int, ctypes.POINTER(WgradMap), P, P, c_int, P], c_int),
         "hiseg_pack_weights": ([P, c_int, c_int, P], c_int),
         "hiseg_bn_partials": ([], c_int),
+        "hiseg_bn_last_path": ([], c_int),
         "hiseg_bn_stats": ([c_int, P, c_ll, c_int, c_int, c_int, P, P], c_int),
         "hiseg_bn_finalize": ([P, c_int, c_ll, P, P, c_float, c_float, P, P, P, P, P, P, P], c_int),
         "hiseg_bn_apply": ([ctypes.POINTER(BnApplyDesc), P], c_int),
@@ -524,6 +525,23 @@ def wgrad_last_path():
     """The kernel of this thread's last hiseg_conv2d_wgrad (a name of WGRAD_PATHS), None before any."""
     v = lib().hiseg_wgrad_last_path()
     return None if v < 0 else WGRAD_PATHS[v]
+
+
+BN_ENTRIES = ("stats", "finalize", "apply", "bwd")
+BN_BWD_MODES = ("none", "y", "relu_pre", "pre")
+
+
+def bn_path_decode(v: int):
+    """The fields of a hiseg_bn_last_path value (include/hiseg_train.h HISEG_BN_PATH_*), None for -1."""
+    if v < 0:
+        return None
+    return {"entry": BN_ENTRIES[v & 3], "vec": bool(v & 4), "par": bool(v & 8), "premerge": bool(v & 16),
+            "mode": BN_BWD_MODES[(v >> 5) & 3], "reduce": bool(v & 128), "u2": bool(v & 256)}
+
+
+def bn_last_path():
+    """Which kernels this thread's last train-mode BatchNorm entry point launched, None before any."""
+    return bn_path_decode(lib().hiseg_bn_last_path())
 
 
 CONV_PATHS = ("generic", "generic_splitk", "fast", "wide", "hw", "hwr", "hwt", "hwc", "pw", "small", "rows")

@@ -111,6 +111,29 @@ typedef struct hiseg_bn_apply_desc {
   int per_sample;                 /* scale / shift are [N][C] per-sample tables (LayerNorm2d), n = p / HW */
 } hiseg_bn_apply_desc;
 int hiseg_bn_apply(const hiseg_bn_apply_desc* d, hiseg_stream_t stream);
+/* Which kernels this thread's last hiseg_bn_stats / _finalize / _finalize_n / _apply / _bwd launched (-1 before any;
+ * a call refused by its argument checks leaves the value as it was; the library's own finalize launches -- the fused
+ * upsample head's statistics, hiseg_ubf_train_fwd -- record FINALIZE too).  Written on the host just before the launches:
+ *   bits 0-1  entry point (HISEG_BN_PATH_STATS / FINALIZE / APPLY / BWD; finalize_n records FINALIZE)
+ *   VEC       stats, apply, bwd: the 16-byte chunk kernels (else the scalar ones)
+ *   PAR       finalize: the one-block-per-channel Chan-tree kernel (else the rows kernel); the backward's
+ *             coefficient kernel has this one form, so bwd always sets it
+ *   PREMERGE  finalize_n, bwd with partial_splits: a group pre-merge launch preceded (more than 256 splits)
+ *   bits 5-6  bwd: how act'(.) is obtained -- 0 none, 1 from the stored y, 2 ReLU mask recomputed at the forward's
+ *             pre-activation, 3 a smooth derivative at the pre-activation
+ *   REDUCE    bwd: the reduction pass over the activations ran (clear with partial_splits > 0)
+ *   U2        apply, bwd (chunk kernels): two pixels per iteration (HISEG_BN_U=2) */
+#define HISEG_BN_PATH_STATS 0
+#define HISEG_BN_PATH_FINALIZE 1
+#define HISEG_BN_PATH_APPLY 2
+#define HISEG_BN_PATH_BWD 3
+#define HISEG_BN_PATH_VEC 4
+#define HISEG_BN_PATH_PAR 8
+#define HISEG_BN_PATH_PREMERGE 16
+#define HISEG_BN_PATH_MODE_SHIFT 5
+#define HISEG_BN_PATH_REDUCE 128
+#define HISEG_BN_PATH_U2 256
+int hiseg_bn_last_path(void);
 
 /* Backward.  g = dy * chan_mul * act'(y) (ReLU: y > 0; sigmoid: y(1-y); SiLU: from the pre-activation
  * xhat*gamma + beta; none: 1), xhat = (z - mean)*invstd:
