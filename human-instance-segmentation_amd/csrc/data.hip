@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "hiseg_data.h"
+#include "roi_gather.h"
 
 namespace hiseg {
 
@@ -70,33 +71,13 @@ __global__ void __launch_bounds__(256) pil_v_kernel(const uint8_t* tmp, int rows
   }
 }
 
-// cv2.resize(..., INTER_NEAREST) source index (OpenCV resizeNN): min(floor(x / (dst / src)), src - 1)
-__device__ __forceinline__ int nn_src(int x, int src, int dst) {
-  const double ifx = 1.0 / ((double)dst / (double)src);
-  const int s = (int)floor((double)x * ifx);
-  return s < src - 1 ? s : src - 1;
-}
-
 __global__ void __launch_bounds__(256) roi_targets_kernel(const uint8_t* masks, const hiseg_roi_target_desc* descs,
                                                           int mh, int mw, long long* out) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
   if (idx >= mh * mw) return;
   const hiseg_roi_target_desc d = descs[b];
-  const int i = idx / mw, j = idx - (idx / mw) * mw;
-  const int rh = d.y2 - d.y1, rw = d.x2 - d.x1;
-  const int yi = d.y1 + nn_src(i, rh, mh), xi = d.x1 + nn_src(j, rw, mw);    // dataset.py:272 (ROI -> mask)
-  const int y0 = nn_src(yi, d.h0, d.img_h), x0 = nn_src(xi, d.w0, d.img_w);  // dataset.py:117 (orig -> image)
-  const long long plane = (long long)d.h0 * d.w0;
-  const uint8_t* m = masks + d.mask_offset + (long long)y0 * d.w0 + x0;
-  long long cls = 0;
-  if (m[(long long)d.target * plane] > 0) {
-    cls = 1;                                                                    // dataset.py:153
-  } else {
-    for (int k = 0; k < d.n_inst; ++k)
-      if (k != d.target && m[(long long)k * plane] > 0) { cls = 2; break; }     // dataset.py:156-160
-  }
-  out[(long long)b * mh * mw + idx] = cls;
+  out[(long long)b * mh * mw + idx] = roi_target_class(masks, d, mh, mw, idx, false);   // csrc/roi_gather.h
 }
 
 inline unsigned nblk(long long n) { return (unsigned)((n + 255) / 256); }

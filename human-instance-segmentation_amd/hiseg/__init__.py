@@ -24,6 +24,7 @@ from .checkpoint import (  # noqa: F401,E402
     load_teacher_checkpoint, resume_distillation_checkpoint, resume_from_checkpoint, save_checkpoint,
     save_distillation_checkpoint)
 from .data import GpuRoiBatchBuilder, resize_bilinear_pil  # noqa: F401,E402
+from .augment import AugParams, RoiSafeAugmentation, augment_images  # noqa: F401,E402
 from .metrics import (  # noqa: F401,E402
     SegmentationMetrics, calculate_confusion_matrix, calculate_detection_metrics, calculate_iou, evaluate_model,
 )

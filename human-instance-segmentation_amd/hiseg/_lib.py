@@ -246,6 +246,12 @@ class RoiTargetDesc(ctypes.Structure):
                                                                  "y2", "img_w", "img_h")]
 
 
+class AugSample(ctypes.Structure):
+    """include/hiseg_augment.h hiseg_aug_sample"""
+    _fields_ = [(n, c_int) for n in ("flip", "hsv", "ksize", "reserved")] + \
+               [("hsv_lut", ctypes.c_ubyte * 256 * 3), ("rgb_lut", ctypes.c_ubyte * 256 * 3), ("kernel", c_float * 49)]
+
+
 class GuidedPrepDesc(Desc):
     """include/hiseg_guided_head.h hiseg_guided_prep_desc"""
     _fields_ = [("mask", c_void_p), ("mask_stride", c_ll), ("N", c_int), ("h", c_int), ("w", c_int), ("dtype", c_int),
@@ -400,6 +406,11 @@ def _declare(lib):
         "hiseg_pil_resample_h": ([P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P], c_int),
         "hiseg_pil_resample_v": ([P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P], c_int),
         "hiseg_roi_targets": ([P, P, c_int, c_int, c_int, P, P], c_int),
+        # ---- ROI-safe training augmentation (include/hiseg_augment.h)
+        "hiseg_aug_struct_size": ([], c_int),
+        "hiseg_aug_validate": ([P, c_int], c_int),
+        "hiseg_augment_fwd": ([P, P, P, c_int, c_int, c_int, P, P], c_int),
+        "hiseg_roi_targets_flip": ([P, P, P, c_int, c_int, c_int, P, P], c_int),
         # ---- mask post-processing (include/hiseg_post.h)
         "hiseg_post_max_iterations": ([c_int, c_int, c_int, c_int], c_int),
         "hiseg_edge_smooth_fwd": ([P, P, c_ll, c_int, c_int, c_float, c_float, c_int, c_int, c_int, P], c_int),

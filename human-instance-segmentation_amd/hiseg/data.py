@@ -1,6 +1,8 @@
 """Training data path on the GPU: COCOInstanceSegmentationDataset.__getitem__
-(src/human_edge_detection/dataset.py:85-291, no augmentation) + convert_batch_format
-(dataset_adapter.py:7-52) for a batch of decoded samples.
+(src/human_edge_detection/dataset.py:85-291) + convert_batch_format (dataset_adapter.py:7-52) for a batch of
+decoded samples; un-augmented by default, or with the reference's ROI-safe training augmentation
+(``GpuRoiBatchBuilder(augment=RoiSafeAugmentation(...))``, hiseg/augment.py: restated, unpinned against
+albumentations and cv2, which are not available to compare against).
 
 The reference decodes, resizes and rasterises every sample on a CPU DataLoader worker (PIL resize, one
 cv2.resize per instance mask to the full image size, numpy masking, another cv2.resize to the mask size).
@@ -20,12 +22,13 @@ from __future__ import annotations
 
 import ctypes
 from functools import lru_cache
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from .augment import AugParams, RoiSafeAugmentation, augment_images, flip_box
 
 
 @lru_cache(maxsize=256)
@@ -122,10 +125,13 @@ def roi_box(bbox: Sequence[float], orig_wh: Tuple[int, int], image_size: Tuple[i
 
 
 def roi_targets(masks: torch.Tensor, descs: List[Tuple[int, int, int, int, int, int, int, int, int]],
-                mask_size: Tuple[int, int], image_size: Tuple[int, int]) -> torch.Tensor:
+                mask_size: Tuple[int, int], image_size: Tuple[int, int],
+                flip: Optional[torch.Tensor] = None) -> torch.Tensor:
     """3-class ROI targets int64 ``[B, mh, mw]`` (dataset.py:117, 149-160, 268-275) for B samples.
     ``masks``: uint8 device buffer holding every sample's instance masks back to back; ``descs``: per sample
-    (mask element offset, n_inst, target, h0, w0, x1, y1, x2, y2) with the ROI in image-size pixels."""
+    (mask element offset, n_inst, target, h0, w0, x1, y1, x2, y2) with the ROI in image-size pixels.
+    ``flip``: device int32 [B]; a flipped sample's ROI is the box of the mirrored image and its target the
+    mirrored ROI crop (dataset.py:180-212, hiseg_roi_targets_flip)."""
     if not masks.is_cuda:
         raise RuntimeError("hiseg data path runs on the GPU only (got a CPU tensor)")
     mh, mw = int(mask_size[0]), int(mask_size[1])
@@ -141,6 +147,13 @@ def roi_targets(masks: torch.Tensor, descs: List[Tuple[int, int, int, int, int, 
     host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
     dev = host.to(masks.device)
     out = torch.empty(B, mh, mw, dtype=torch.int64, device=masks.device)
+    if flip is not None:
+        if flip.dtype != torch.int32 or tuple(flip.shape) != (B,) or flip.device != masks.device:
+            raise ValueError("roi_targets: flip must be int32 [B] on the masks' device")
+        L.check(L.lib().hiseg_roi_targets_flip(masks.data_ptr(), dev.data_ptr(), flip.data_ptr(), B, mh, mw,
+                                               out.data_ptr(), L.stream_ptr()), "roi_targets_flip")
+        dev.record_stream(torch.cuda.current_stream(masks.device))
+        return out
     L.check(L.lib().hiseg_roi_targets(masks.data_ptr(), dev.data_ptr(), B, mh, mw, out.data_ptr(), L.stream_ptr()),
             "roi_targets")
     dev.record_stream(torch.cuda.current_stream(masks.device))
@@ -155,10 +168,21 @@ class GpuRoiBatchBuilder:
     original pixels, 'target': index of the target instance, 'image_id' (optional)} returns
     {'image' f32 [B, 3, H, W], 'roi_boxes' f32 [B, 5], 'roi_masks' int64 [B, mh, mw], 'instance_info'} on the
     device, with the reference's values.  Constructor arguments as the reference dataset's (mask_size is
-    (height, width); image_size is (width, height), as PIL / cv2 take it)."""
+    (height, width); image_size is (width, height), as PIL / cv2 take it).
+
+    ``augment``: None (the un-augmented batch) or a ``hiseg.RoiSafeAugmentation``.  With one, the images are
+    resized to 8 bits and ``augment_images`` flips, recolours, blurs and normalises them in one launch; a flipped
+    sample's ROI becomes (W - x2, y1, W - x1, y2) in exact integers, ``roi_boxes`` is normalised from that box
+    and its ROI target is the mirrored ROI crop (hiseg_roi_targets_flip); the batch gains ``'aug_params'``, the
+    drawn ``AugParams``.  The reference sends the box through albumentations' normalised float coordinates and
+    back before truncating it (dataset.py:196-198); that float round trip is not reproduced."""
 
     def __init__(self, device="cuda", mask_size: Tuple[int, int] = (56, 56), image_size: Tuple[int, int] = (640, 640),
-                 roi_padding: float = 0.0, min_roi_size: int = 16, feature_size: Tuple[int, int] = (80, 80)):
+                 roi_padding: float = 0.0, min_roi_size: int = 16, feature_size: Tuple[int, int] = (80, 80),
+                 augment: Optional[RoiSafeAugmentation] = None):
+        if augment is not None and not isinstance(augment, RoiSafeAugmentation):
+            raise TypeError("GpuRoiBatchBuilder: augment must be a RoiSafeAugmentation or None")
+        self.augment = augment
         self.device = torch.device(device)
         self.mask_size = tuple(mask_size) if isinstance(mask_size, (tuple, list)) else (mask_size, mask_size)
         self.image_size, self.roi_padding, self.min_roi_size = tuple(image_size), roi_padding, min_roi_size
@@ -169,18 +193,24 @@ class GpuRoiBatchBuilder:
         B = len(samples)
         imgs = [torch.as_tensor(s["image"]) for s in samples]
         # images: one batched resample per distinct source size
-        out = torch.empty(B, 3, self.image_size[1], self.image_size[0], dtype=torch.float32, device=dev)
+        aug: Optional[AugParams] = None if self.augment is None else self.augment.sample(B).to(dev)
+        if aug is None:
+            out = torch.empty(B, 3, self.image_size[1], self.image_size[0], dtype=torch.float32, device=dev)
+        else:
+            out = torch.empty(B, self.image_size[1], self.image_size[0], 3, dtype=torch.uint8, device=dev)
         by_size: Dict[Tuple[int, int], List[int]] = {}
         for i, im in enumerate(imgs):
             by_size.setdefault(tuple(im.shape), []).append(i)
         for shape, idx in by_size.items():
             batch = torch.stack([imgs[i] for i in idx]).to(dev, non_blocking=True)
-            res = resize_bilinear_pil(batch, self.image_size)
+            res = resize_bilinear_pil(batch, self.image_size, out_f32=aug is None)
             out[torch.tensor(idx, device=dev)] = res
+        if aug is not None:
+            out = augment_images(out, aug, mode="normalize")
         # ROI boxes (host arithmetic, dataset.py:122-147, 163-168) and the instance masks in one buffer
         descs, chunks, norms = [], [], []
         off = 0
-        for s, im in zip(samples, imgs):
+        for i, (s, im) in enumerate(zip(samples, imgs)):
             m = torch.as_tensor(s["instance_masks"])
             k, h0, w0 = m.shape
             oh, ow = im.shape[0], im.shape[1]
@@ -188,14 +218,19 @@ class GpuRoiBatchBuilder:
                 raise ValueError("instance masks must have the decoded image's size (annToMask)")
             x1, y1, x2, y2 = roi_box(s["bboxes"][s["target"]], (ow, oh), self.image_size, self.roi_padding,
                                      self.min_roi_size)
+            if aug is not None and aug.host["flip"][i]:
+                x1, y1, x2, y2 = flip_box((x1, y1, x2, y2), self.image_size[0])
             descs.append((off, k, int(s["target"]), h0, w0, x1, y1, x2, y2))
             chunks.append(m.reshape(-1).to(torch.uint8))
             off += m.numel()
             norms.append(np.array([x1 / self.image_size[0], y1 / self.image_size[1], x2 / self.image_size[0],
                                    y2 / self.image_size[1]], dtype=np.float32))
         masks = torch.cat(chunks).to(dev, non_blocking=True)
-        roi_masks = roi_targets(masks, descs, self.mask_size, self.image_size)
+        roi_masks = roi_targets(masks, descs, self.mask_size, self.image_size, None if aug is None else aug.flip)
         roi_boxes = torch.tensor([[i, *n.tolist()] for i, n in enumerate(norms)], dtype=torch.float32).to(dev)
         info = [{"image_id": s.get("image_id", 0), "instance_masks": [],
                  "instance_distances": torch.zeros(self.mask_size, dtype=torch.float32, device=dev)} for s in samples]
-        return {"image": out, "roi_boxes": roi_boxes, "roi_masks": roi_masks, "instance_info": info}
+        batch = {"image": out, "roi_boxes": roi_boxes, "roi_masks": roi_masks, "instance_info": info}
+        if aug is not None:
+            batch["aug_params"] = aug
+        return batch

@@ -1,6 +1,8 @@
 /*
  * hiseg_data.h — the training data path on the GPU (src/human_edge_detection/dataset.py:85-291
- * COCOInstanceSegmentationDataset.__getitem__ without augmentation, dataset_adapter.py:7-52 collate).
+ * COCOInstanceSegmentationDataset.__getitem__, dataset_adapter.py:7-52 collate).  These entry points build the
+ * un-augmented batch; the reference's ROI-safe training augmentation runs on their 8-bit output through
+ * hiseg_augment.h (hiseg_augment_fwd, hiseg_roi_targets_flip: albumentations / cv2 restated, unpinned).
  * Conventions as in hiseg.h.  Decoding (PIL / pycocotools on the host) stays outside: these entry points
  * take decoded 8-bit images and per-instance binary masks and produce, for a batch of samples,
  *   - the image resized to the training size exactly as PIL Image.resize(size, BILINEAR) (Pillow
