@@ -36,6 +36,10 @@ int conv_pw_gate_images(const ConvArgs& a);
 bool conv_rows_form(const ConvArgs& a);
 int conv_hwc_stats_tiles(const ConvArgs& a);
 int conv_hwc_fused_variant(const ConvArgs& a, bool r3);
+// The fused 64-channel ResidualBlock (conv_resblock.hip): whether the pair of layers has its form; its launch (a
+// HISEG_* status; the caller checked conv_resblock_applies)
+bool conv_resblock_applies(const hiseg_conv2d_desc& d1, const hiseg_conv2d_desc& d2);
+int conv_resblock_launch(const hiseg_conv2d_desc& d1, const hiseg_conv2d_desc& d2, hipStream_t s);
 // The generic kernel (conv_igemm.hip), any dtype pair; splits > 1: its split-K form (a.kper K blocks per split, a.ws
 // the workspace).  *bco: the Cout tile it launched.  Returns a HISEG_* status.
 int conv_generic_launch(const ConvArgs& a, hipStream_t s, int splits, int* bco);

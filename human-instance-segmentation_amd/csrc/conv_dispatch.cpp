@@ -422,6 +422,22 @@ static int conv2d_impl(const hiseg_conv2d_desc* d, hiseg_stream_t stream, int va
   return conv_in_ranges(d, s, variant);
 }
 
+// ---------------------------------------------------------------------------------------- fused ResidualBlock
+// Two layers in one launch (conv_resblock.hip).  Not a candidate of the automatic choice: the caller holds both
+// descriptors, asks hiseg_resblock_fused_ok and otherwise launches the layers one by one.
+extern "C" int hiseg_resblock_fused_ok(const hiseg_conv2d_desc* d1, const hiseg_conv2d_desc* d2) {
+  return d1 != nullptr && d2 != nullptr && conv_resblock_applies(*d1, *d2) ? 1 : 0;
+}
+
+extern "C" int hiseg_resblock_fwd(const hiseg_conv2d_desc* d1, const hiseg_conv2d_desc* d2, hiseg_stream_t stream) {
+  HISEG_REQUIRE(d1 != nullptr && d2 != nullptr, HISEG_ERR_BAD_ARG, "resblock: null descriptor");
+  HISEG_REQUIRE(conv_resblock_applies(*d1, *d2), HISEG_ERR_BAD_ARG,
+                "resblock: the pair of layers has no fused kernel (hiseg_resblock_fused_ok)");
+  const int r = conv_resblock_launch(*d1, *d2, (hipStream_t)stream);
+  if (r == HISEG_OK) conv_note_path(HISEG_CONV_PATH_RESBLOCK, 1);
+  return r;
+}
+
 extern "C" int hiseg_conv2d_fwd(const hiseg_conv2d_desc* d, hiseg_stream_t stream) {
   return conv2d_impl(d, stream, 0);
 }

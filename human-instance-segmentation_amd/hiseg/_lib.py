@@ -307,6 +307,8 @@ def _declare(lib):
         "hiseg_attn_map_fwd": ([c_int, P, c_int, c_int, c_int, c_int, P, c_int, P, P, P], c_int),
         "hiseg_pixel_scale_fwd": ([c_int, P, c_ll, c_int, P, P, P], c_int),
         "hiseg_conv2d_fused_ok": ([ctypes.POINTER(Conv2dDesc)], c_int),
+        "hiseg_resblock_fused_ok": ([ctypes.POINTER(Conv2dDesc), ctypes.POINTER(Conv2dDesc)], c_int),
+        "hiseg_resblock_fwd": ([ctypes.POINTER(Conv2dDesc), ctypes.POINTER(Conv2dDesc), P], c_int),
         "hiseg_hier_combine_tn_fwd": ([P, c_int, c_int, c_int, P, P, P, P, c_int, c_float, c_int, P, P, P, P, P, P],
                                       c_int),
         "hiseg_gap_splits": ([c_int], c_int),
@@ -555,7 +557,7 @@ def bn_last_path():
     return bn_path_decode(lib().hiseg_bn_last_path())
 
 
-CONV_PATHS = ("generic", "generic_splitk", "fast", "wide", "hw", "hwr", "hwt", "hwc", "pw", "small", "rows")
+CONV_PATHS = ("generic", "generic_splitk", "fast", "wide", "hw", "hwr", "hwt", "hwc", "pw", "small", "rows", "resblock")
 
 
 def conv_last_path():

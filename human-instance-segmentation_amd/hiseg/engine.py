@@ -160,6 +160,11 @@ def _check_input(x: torch.Tensor, what: str):
 
 
 # ------------------------------------------------------------------------------------ blocks
+# residual_block takes the one-launch form of a 64-channel block (ops.resblock) where the library has it; False runs
+# every block as two launches (the tests' bit-for-bit comparison; not a setting of the product)
+RESBLOCK_FUSED = True
+
+
 def _block_acts(blk: nn.Module) -> Tuple[int, int]:
     return (act_code(blk.activation1 if hasattr(blk, "activation1") else blk.activation),
             act_code(blk.activation2 if hasattr(blk, "activation2") else blk.activation))
@@ -181,11 +186,19 @@ def gated_block_ok(E: Ctx, blk: nn.Module, x: Act, gate: torch.Tensor, head2: op
 
 def residual_block(E: Ctx, blk: nn.Module, x: Act, out: Optional[Act] = None,
                    head2: Optional[ops.Head2] = None, in_gate: Optional[torch.Tensor] = None) -> Optional[Act]:
-    """ResidualBlock (refinement.py:31-55 / unet.py:35-58): two fused launches.  ``head2``: a 1x1 -> 2 that alone
+    """ResidualBlock (refinement.py:31-55 / unet.py:35-58): one launch for the 64-channel bf16 form
+    (ops.resblock), else two fused launches.  ``head2``: a 1x1 -> 2 that alone
     consumes the block's output (ops.Head2); returns None when conv2's epilogue applied it.  ``in_gate`` (f32
     [N, C]): the block's input is x * in_gate[image][channel], applied by both convs as they read x (the caller
     checked gated_block_ok)."""
     a1, a2 = _block_acts(blk)
+    if RESBLOCK_FUSED and in_gate is None and head2 is None and out is None and x.C == 64 and \
+            x.dtype == torch.bfloat16 and not isinstance(blk.norm1, LayerNorm2d) and \
+            not isinstance(blk.norm2, LayerNorm2d):
+        # the 64-channel blocks: one launch, the intermediate stays on the compute unit (the same bits)
+        y = ops.resblock(E.conv(blk.conv1, blk.norm1, a1), E.conv(blk.conv2, blk.norm2, a2), x)
+        if y is not None:
+            return y
     if in_gate is not None:
         h = ops.conv2d(E.conv(blk.conv1, blk.norm1, a1), x, a_gate=in_gate)
         return ops.conv2d(E.conv(blk.conv2, blk.norm2, a2), h, residual=x, res_gate=in_gate, head2=head2)

@@ -456,6 +456,23 @@ def _fused_ok(p, xa, xb, residual, mul, in_scale, px_scale, head2, out_dtype, a_
     return bool(L.lib().hiseg_conv2d_fused_ok(ctypes.byref(d)))
 
 
+def resblock(p1: ConvPlan, p2: ConvPlan, x: Act) -> Optional[Act]:
+    """A 64-channel ResidualBlock act2(conv2(act1(conv1(x))) + x) in one launch (hiseg_resblock_fwd): the bits of
+    conv2d(p2, conv2d(p1, x), residual=x), the intermediate never stored.  Returns None -- nothing launched -- where
+    the library has no such kernel for the pair (hiseg_resblock_fused_ok) or a launch hook (RECORD, GATE) wants the
+    layers one by one; the caller then runs the two launches."""
+    if RECORD is not None or GATE is not None or x.dtype != torch.bfloat16 or p1.convT or p2.convT or \
+            p1.cout != 64 or p2.cout != 64 or x.C != 64:
+        return None
+    out = Act.new(x.N, x.H, x.W, p2.cout, x.dtype, x.t.device, zero=None)
+    d1 = _conv_desc(p1, x, None, None, None, None, out_dtype=x.dtype)
+    d2 = _conv_desc(p2, x, None, x, None, out)   # (srcA stands in for the intermediate: same shape, never read)
+    if not L.lib().hiseg_resblock_fused_ok(ctypes.byref(d1), ctypes.byref(d2)):
+        return None
+    L.check(L.lib().hiseg_resblock_fwd(ctypes.byref(d1), ctypes.byref(d2), L.stream_ptr()), "resblock")
+    return out
+
+
 def _launch_conv(d, p, xa, xb, variant=0):
     if PROBE is not None:
         key = PROBE.select(d)

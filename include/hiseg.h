@@ -184,6 +184,17 @@ int hiseg_conv2d_fwd(const hiseg_conv2d_desc* d, hiseg_stream_t stream);
  * (hiseg_pixel_scale_fwd / hiseg_channel_scale_fwd before the conv; the conv, then hiseg_hier_combine_fwd on its
  * output). */
 int hiseg_conv2d_fused_ok(const hiseg_conv2d_desc* d);
+/* A whole 64-channel ResidualBlock, y = act2(bn2(conv2(act1(bn1(conv1(x))))) + x), in one launch: d1 describes conv1
+ * (srcA = x, no residual; its `out` is not written), d2 conv2 (residual = x with conv1's source stride and offset,
+ * out = y; its srcA, the intermediate, is never read or written).  The intermediate stays on the compute unit as
+ * the bf16 tensor conv1 would have stored, so y equals hiseg_conv2d_fwd(d1) followed by hiseg_conv2d_fwd(d2) bit for
+ * bit.  The form: bf16, both layers 3x3 / stride 1 / pad 1 with 64 input and 64 output channels and weight_frag,
+ * activations none or ReLU, no second source, gate, mul, out2, head2, fused statistics or workspace, a dense
+ * 64-channel `out` that is not x, operands under 2 GiB.  hiseg_resblock_fused_ok: 1 when the pair has that form (no
+ * launch); hiseg_resblock_fwd fails where it returns 0.  The launch is recorded as path
+ * HISEG_CONV_PATH_RESBLOCK * 10000 + 1. */
+int hiseg_resblock_fused_ok(const hiseg_conv2d_desc* d1, const hiseg_conv2d_desc* d2);
+int hiseg_resblock_fwd(const hiseg_conv2d_desc* d1, const hiseg_conv2d_desc* d2, hiseg_stream_t stream);
 /* sizeof of every descriptor struct of the C ABI, in the order roi_align_desc, conv2d_desc, wgrad_map, pack_entry,
  * bn_apply_desc, bn_bwd_desc, ln_bwd_desc, ew_view, ubf_desc, ubf_grads, loss_cfg, distill_cfg, roi_target_desc
  * (the first n of them into out); returns their count.  Bindings check their struct layouts against it. */
@@ -217,7 +228,8 @@ int hiseg_conv2d_fwd_variant(const hiseg_conv2d_desc* d, int variant, hiseg_stre
 #define HISEG_CONV_PATH_PW 8
 #define HISEG_CONV_PATH_SMALL 9
 #define HISEG_CONV_PATH_ROWS 10
-#define HISEG_CONV_PATH_FAMILIES 11
+#define HISEG_CONV_PATH_RESBLOCK 11
+#define HISEG_CONV_PATH_FAMILIES 12
 int hiseg_conv2d_last_path(void);
 int hiseg_conv2d_path_stats(long long* counts, int n, int reset);
 

@@ -114,14 +114,71 @@ def run(d, v):
     L.check(L.lib().hiseg_conv2d_fwd_variant(ctypes.byref(d), v, L.stream_ptr()), f"conv variant {v}")
 
 
+def resblock_bench(args):
+    """--resblock: the fused 64-channel ResidualBlock (hiseg_resblock_fwd) against the pair it replaces -- plain conv1,
+    then conv2 with the residual, the automatic choice -- interleaved in one process, best round; bit-equality of the
+    outputs; ms, TFLOP/s on the pair's algorithmic FLOPs, algorithmic GB/s (pair: x, h out, h in, x, y = 5 tensors;
+    fused: x in, y out = 2)."""
+    N, C, H, W = 256, 64, 64, 48
+    dt = torch.bfloat16
+    g = torch.Generator(device=DEV).manual_seed(0)
+    x = ops.Act.new(N, H, W, C, dt, DEV, zero=False)
+    x.t.copy_(torch.randn(x.t.numel(), device=DEV, generator=g))
+    plans = []
+    for _ in range(2):
+        w = torch.randn(C, C, 3, 3, device=DEV, generator=g) / (9 * C) ** 0.5
+        plans.append(ops.pack_conv(w, torch.randn(C, device=DEV, generator=g) * 0.1, None, 1, dt, DEV, pad=1))
+    h, y2, y1 = (ops.Act.new(N, H, W, C, dt, DEV, zero=False) for _ in range(3))
+    da, db = desc(plans[0], x, None, None, h), desc(plans[1], h, None, x, y2)
+    f1, f2 = desc(plans[0], x, None, None, h), desc(plans[1], h, None, x, y1)
+    assert L.lib().hiseg_resblock_fused_ok(ctypes.byref(f1), ctypes.byref(f2)), "the block must have the fused form"
+
+    def pair():
+        L.check(L.lib().hiseg_conv2d_fwd(ctypes.byref(da), L.stream_ptr()), "conv1")
+        L.check(L.lib().hiseg_conv2d_fwd(ctypes.byref(db), L.stream_ptr()), "conv2")
+
+    def fused():
+        L.check(L.lib().hiseg_resblock_fwd(ctypes.byref(f1), ctypes.byref(f2), L.stream_ptr()), "resblock")
+
+    y1.t.fill_(float("nan"))
+    y2.t.fill_(float("nan"))
+    pair()
+    fused()
+    torch.cuda.synchronize()
+    same = bool(torch.equal(y1.t, y2.t))
+    times = {"pair": [], "fused": []}
+    for _ in range(args.rounds):
+        for name, fn in (("pair", pair), ("fused", fused)):
+            for _ in range(3):
+                fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) / args.reps)
+    flops = 2 * 2.0 * N * H * W * C * 9 * C
+    tensor = 2.0 * N * H * W * C
+    row = {"bit_equal": same}
+    for name, nt in (("pair", 5), ("fused", 2)):
+        ms = min(times[name])
+        row[name] = {"ms": round(ms, 4), "tflops": round(flops / ms / 1e9, 1), "alg_gbs": round(nt * tensor / ms / 1e6, 1),
+                     "rounds_ms": [round(v, 4) for v in times[name]]}
+    print("resblock64_64x48", json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--resblock", action="store_true", help="time the fused 64-channel ResidualBlock against its pair")
     ap.add_argument("--variants", default="-1,0,1,2,4")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--bitref", type=int, default=None, help="also report bit-equality against this variant")
     args = ap.parse_args()
+    if args.resblock:
+        return resblock_bench(args)
     variants = [int(v) for v in args.variants.split(",")]
     results = {}
     for name in args.shapes.split(","):
