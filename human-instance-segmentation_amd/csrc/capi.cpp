@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
+#include "gfx950_prims.h"
 #include "hiseg.h"
 #include "hiseg_data.h"
 #include "hiseg_distill.h"
@@ -78,6 +79,17 @@ extern "C" int hiseg_guided_struct_sizes(long long* out, int n) {
   const int m = (int)(sizeof(sz) / sizeof(sz[0]));
   for (int i = 0; i < n && i < m; ++i) out[i] = sz[i];
   return m;
+}
+
+// The kernels' XCD-major workgroup remap on the host (no launch): the same function, for tests/test_xcd_remap.py
+extern "C" int hiseg_xcd_major(int block, int nblocks) { return hiseg::xcd_major(block, nblocks); }
+extern "C" int hiseg_xcd_major_fill(int nblocks, int first, int count, int* out) {
+  if (!out || nblocks < 1 || first < 0 || count < 0 || count > nblocks - first) {
+    hiseg_set_error("xcd_major_fill: bad args");
+    return HISEG_ERR_BAD_ARG;
+  }
+  for (int i = 0; i < count; ++i) out[i] = hiseg::xcd_major(first + i, nblocks);
+  return HISEG_OK;
 }
 
 extern "C" int hiseg_version(void) { return 100; }

@@ -1,11 +1,9 @@
 // Shared pieces of the implicit-GEMM conv kernels (GEMM view, epilogue).
 #pragma once
 #include "common.h"
+#include "gfx950_prims.h"
 
 namespace hiseg {
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 struct ConvArgs {
   hiseg_conv2d_desc d;

@@ -19,18 +19,6 @@
 
 namespace hiseg {
 
-typedef __attribute__((address_space(3))) void lds_void;
-
-// One 16-B-per-lane LDS-DMA (1 KiB per wave instruction) written as inline asm so that hipcc's
-// waitcnt pass does not see it: the compiler would otherwise drain vmcnt(0) before the first
-// ds_read after every issue (LDS-DMA writes alias the LDS the MFMAs read), which serialises the
-// ring.  Completion is tracked by the explicit counted s_waitcnt vmcnt in the K loop
-// (cdna_hip_programming.md §5.7 item 1).  M0 is written inside the same statement.
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned lds_addr, unsigned voff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-               :: "s"(lds_addr), "v"(voff), "s"(rsrc) : "memory");
-}
-
 // STAMP (diagnostic builds only): wave 0 lane 0 writes s_memtime at kernel entry, loop entry,
 // loop exit and kernel exit to the u64 buffer passed in desc.out2 (4 per workgroup) and skips
 // the out2 store; outputs are otherwise unchanged.
@@ -72,10 +60,7 @@ __global__ void __launch_bounds__(64 * WCO * WPX) conv_fast_kernel(ConvArgs a) {
 
   // ---- XCD-major bijective remap, Cout tiles fastest
   const int nco = d.Cout_pad / BCO;
-  const int nwg = gridDim.x;
-  const int orig = blockIdx.x;
-  const int q = nwg >> 3, r8 = nwg & 7, xcd = orig & 7, loc = orig >> 3;
-  const int wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + loc;
+  const int wg = xcd_major(blockIdx.x, gridDim.x);
   const int co0 = (wg % nco) * BCO;
   const int px0 = (wg / nco) * BPX;
 
@@ -108,10 +93,9 @@ __global__ void __launch_bounds__(64 * WCO * WPX) conv_fast_kernel(ConvArgs a) {
     woff[i] = ((unsigned)(co0 + r) * (unsigned)d.K_pad + (unsigned)c * 8u) * 2u;
   }
 
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(d.srcA), (short)0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(d.srcB ? d.srcB : d.srcA), (short)0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(d.weight), (short)0, 0x7fffffff, 0x00020000);
-  const unsigned OOB = 0x80000000u;  // >= num_records: the DMA returns zeros
+  const __amdgpu_buffer_rsrc_t rA = buf_rsrc(d.srcA, 0x7fffffff);
+  const __amdgpu_buffer_rsrc_t rB = buf_rsrc(d.srcB ? d.srcB : d.srcA, 0x7fffffff);
+  const __amdgpu_buffer_rsrc_t rW = buf_rsrc(d.weight, 0x7fffffff);
 
   const int Cin = a.Cin;
   const int bpt = (Cin + 63) >> 6;  // K blocks per tap (a 1x1 layer's src-B tail block is partial)
@@ -132,15 +116,15 @@ __global__ void __launch_bounds__(64 * WCO * WPX) conv_fast_kernel(ConvArgs a) {
       const int iy = piy[i] + ky, ix = pix[i] + kx;
       const bool ok = (unsigned)iy < (unsigned)d.H && (unsigned)ix < (unsigned)d.W &&
                       (fromA || ci0 - d.Ca + pch[i] * 8 < d.Cb);
-      const unsigned off = ok ? ((unsigned)((pidx[i] + dpix) * cs + cbase) + (unsigned)pch[i] * 8u) * 2u : OOB;
+      const unsigned off = ok ? ((unsigned)((pidx[i] + dpix) * cs + cbase) + (unsigned)pch[i] * 8u) * 2u : kOobOffset;
       const unsigned dst = sbase + (unsigned)(BCO * 8 + 8 * 8 * (w + NW * i)) * 16u;
-      dma16(fromA ? rA : rB, dst, off);
+      lds_dma16(fromA ? rA : rB, dst, off);
     }
     const unsigned kofs = (unsigned)kb * 128u;
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
       const unsigned dst = sbase + (unsigned)(8 * 8 * (w + NW * i)) * 16u;
-      dma16(rW, dst, woff[i] + kofs);
+      lds_dma16(rW, dst, woff[i] + kofs);
     }
   };
 
@@ -171,8 +155,8 @@ __global__ void __launch_bounds__(64 * WCO * WPX) conv_fast_kernel(ConvArgs a) {
     // loads of block kb are done once at most (STAGES-2) younger stages are outstanding
     if (kb + STAGES - 2 < nK) {
       if constexpr (STAGES == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else if constexpr (STAGES == 3) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NL) : "memory");
-      else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * NL) : "memory");
+      else if constexpr (STAGES == 3) vm_wait<NL>();
+      else vm_wait<2 * NL>();
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }

@@ -34,21 +34,6 @@
 
 namespace hiseg {
 
-typedef __attribute__((address_space(3))) void lds_void_h;
-
-__device__ __forceinline__ void dma16h(__amdgpu_buffer_rsrc_t rsrc, unsigned lds_addr, unsigned voff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-               :: "s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff), "s"(rsrc) : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void hvm() {
-  asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
-}
-
-__device__ __forceinline__ int hwswz(int r) { return (-(r >> 2)) & 3; }        // weight rows (16-aligned reads)
-__device__ __forceinline__ int hhswz(int r) { return ((r >> 2) & 1) << 1; }     // halo rows (any start)
-
 constexpr int kHaloRows = 324;             // 18 x 18
 constexpr int kHaloBytes = 24 * 1024;      // 24 pieces of 16 rows x 64 B (rows 324..383: padding)
 
@@ -79,10 +64,7 @@ __global__ void __launch_bounds__(256, 1) conv_hw_kernel(ConvArgs a) {
   // ---- XCD-major bijective remap; Cout tiles fastest, then the 16 x 16 pixel tiles of an image row-major
   const int nco = (d.Cout_pad + BCO - 1) / BCO;   // (BCO 64 over 16 / 32 / 48 columns: one partial tile)
   const int ntx = (d.W + 15) >> 4, nty = (d.H + 15) >> 4;
-  const int nwg = gridDim.x;
-  const int orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7, loc = orig >> 3;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+  const int wg = xcd_major(blockIdx.x, gridDim.x);
   const int co0 = (wg % nco) * BCO;
   int tl = wg / nco;
   const int tx = tl % ntx;
@@ -97,11 +79,10 @@ __global__ void __launch_bounds__(256, 1) conv_hw_kernel(ConvArgs a) {
 #pragma unroll
   for (int i = 0; i < NAI; ++i) {
     const int r = 16 * (w + 4 * i) + lrow;
-    woff[i] = ((unsigned)(co0 + r) * (unsigned)d.K_pad + (unsigned)((slot ^ hwswz(r)) * 8)) * 2u;
+    woff[i] = ((unsigned)(co0 + r) * (unsigned)d.K_pad + (unsigned)((slot ^ weight_row_swz(r)) * 8)) * 2u;
   }
-  const unsigned OOB = 0x80000000u;   // >= num_records: the DMA returns zeros
   // halo rows: piece h (0..23) = rows 16h + lane / 4; piece 4p + w belongs to wave w (p = 0..5).  The lane's
-  // byte offset for piece p (slice 0; OOB outside the image / past row 324), computed where needed: a
+  // byte offset for piece p (slice 0; kOobOffset outside the image / past row 324), computed where needed: a
   // precomputed array indexed by the stage's piece number would live in scratch
   // slice sl of a two-source layer (the EnhancedUNet decoder concat) comes from src B once 32 sl >= Ca
   auto halo_off = [&](int p, int sl) __attribute__((always_inline)) -> unsigned {
@@ -115,29 +96,26 @@ __global__ void __launch_bounds__(256, 1) conv_hw_kernel(ConvArgs a) {
     // source pixel (iy / 2, ix / 2) of the (H / 2, W / 2) grid
     const int ush = (!fb && d.a_up == 2) ? 1 : 0;
     const int sy = iy >> ush, sx = ix >> ush, sH = d.H >> ush, sW = d.W >> ush;
-    return ok ? (unsigned)((((n * sH + sy) * sW + sx) * cs + coff + (slot ^ hhswz(hr)) * 8) * 2) : OOB;
+    return ok ? (unsigned)((((n * sH + sy) * sW + sx) * cs + coff + (slot ^ halo_row_swz(hr)) * 8) * 2) : kOobOffset;
   };
   const int nrec_w = d.Cout_pad * d.K_pad * 2;
   const int nrec_a = d.N * (d.H / d.a_up) * (d.W / d.a_up) * d.a_cstride * 2;
   const int nrec_b = d.Cb ? d.N * d.H * d.W * d.b_cstride * 2 : 0;
   const int nsl = a.Cin >> 5;          // 32-channel slices
   const int nS = 9 * nsl;
-  const unsigned lds_base = (unsigned)(uintptr_t)(lds_void_h*)smem;
+  const unsigned lds_base = (unsigned)(uintptr_t)(lds_void*)smem;
   const unsigned halo_base = lds_base + (unsigned)RING;
-  const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(d.weight), (short)0, nrec_w,
-                                                                     0x00020000);
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(d.srcA), (short)0, nrec_a,
-                                                                     0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(d.Cb ? d.srcB : d.srcA), (short)0,
-                                                                     nrec_b, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rW = buf_rsrc(d.weight, nrec_w);
+  const __amdgpu_buffer_rsrc_t rA = buf_rsrc(d.srcA, nrec_a);
+  const __amdgpu_buffer_rsrc_t rB = buf_rsrc(d.Cb ? d.srcB : d.srcA, nrec_b);
 
   // ---- the DMA set to be issued next: stage (n_sl, n_tap); weights of that stage, plus, for taps 3..8 of
   // every slice but the last, halo piece (tap - 3) of slice n_sl + 1
   int n_sl = 0, n_tap = 0;
-  unsigned p_sbase = lds_base, p_voff[NAI], p_hdst = halo_base, p_hoff = OOB;
+  unsigned p_sbase = lds_base, p_voff[NAI], p_hdst = halo_base, p_hoff = kOobOffset;
   bool p_halo = false, p_hb = false;
 #pragma unroll
-  for (int k = 0; k < NAI; ++k) p_voff[k] = OOB;
+  for (int k = 0; k < NAI; ++k) p_voff[k] = kOobOffset;
   auto prepare_live = [&](int s) __attribute__((always_inline)) {
     p_sbase = lds_base + (unsigned)((s & (STAGES - 1)) * STAGE_BYTES);
     const int wtap = REUSE ? (n_tap % 3) * 3 + n_tap / 3 : n_tap;   // packed weights: tap = ky * 3 + kx
@@ -157,7 +135,7 @@ __global__ void __launch_bounds__(256, 1) conv_hw_kernel(ConvArgs a) {
   auto prepare_dead = [&](int s) __attribute__((always_inline)) {
     p_sbase = lds_base + (unsigned)((s & (STAGES - 1)) * STAGE_BYTES);
 #pragma unroll
-    for (int k = 0; k < NAI; ++k) p_voff[k] = OOB;
+    for (int k = 0; k < NAI; ++k) p_voff[k] = kOobOffset;
     p_halo = false;
   };
   auto prepare = [&](int s) __attribute__((always_inline)) {
@@ -168,9 +146,9 @@ __global__ void __launch_bounds__(256, 1) conv_hw_kernel(ConvArgs a) {
   auto slot_dma = [&](auto kc) __attribute__((always_inline)) {
     constexpr int k = decltype(kc)::value;
     if constexpr (k < NAI) {
-      dma16h(rW, p_sbase + (unsigned)(1024 * (w + 4 * k)), p_voff[k]);
+      lds_dma16(rW, p_sbase + (unsigned)(1024 * (w + 4 * k)), p_voff[k]);
     } else if constexpr (k == NAI) {
-      if (p_halo) dma16h(p_hb ? rB : rA, p_hdst, p_hoff);
+      if (p_halo) lds_dma16(p_hb ? rB : rA, p_hdst, p_hoff);
     }
   };
   // halo of a set: the hand-over waits count one DMA more when the set following the awaited one carries one
@@ -182,7 +160,7 @@ __global__ void __launch_bounds__(256, 1) conv_hw_kernel(ConvArgs a) {
   // ---- fragment reads.  A: weight ring (16-aligned rows).  B: pixel (row j of the wave's 8 tile rows, column
   // lane % 16) at tap (ky, kx) = halo row (wpx*8 + j + ky) * 18 + (lane % 16) + kx, chunk lane / 16
   const char* lds_c = reinterpret_cast<const char*>(smem);
-  const int a_lane_off = (lane & 15) * 64 + (((lane >> 4) ^ hwswz(lane & 15)) << 4);
+  const int a_lane_off = (lane & 15) * 64 + (((lane >> 4) ^ weight_row_swz(lane & 15)) << 4);
   auto rdA = [&](int s, int i) __attribute__((always_inline)) {
     return *reinterpret_cast<const uint4*>(lds_c + (s & (STAGES - 1)) * STAGE_BYTES + (wco * TM * 16 + i * 16) * 64 +
                                            a_lane_off);
@@ -191,7 +169,7 @@ __global__ void __launch_bounds__(256, 1) conv_hw_kernel(ConvArgs a) {
   // B fragment of halo tile row k (= output tile row + ky) at column shift kx
   auto rdBk = [&](int sl, int kx, int k) __attribute__((always_inline)) {
     const int hr = (wpx * TN + k) * 18 + bcol + kx;
-    return *reinterpret_cast<const uint4*>(lds_c + RING + (sl & 1) * kHaloBytes + hr * 64 + ((bch ^ hhswz(hr)) << 4));
+    return *reinterpret_cast<const uint4*>(lds_c + RING + (sl & 1) * kHaloBytes + hr * 64 + ((bch ^ halo_row_swz(hr)) << 4));
   };
   auto rdB = [&](int sl, int tap, int j) __attribute__((always_inline)) {
     const int ky = tap / 3, kx = tap - 3 * (tap / 3);
@@ -207,7 +185,7 @@ __global__ void __launch_bounds__(256, 1) conv_hw_kernel(ConvArgs a) {
   // ---- prologue: slice 0's halo (6 pieces per wave), sets 0 and 1 whole, slots 0..1 of set 2
 #pragma unroll
   for (int p = 0; p < 6; ++p)
-    dma16h(rA, halo_base + (unsigned)(1024 * (4 * p + w)), halo_off(p, 0));
+    lds_dma16(rA, halo_base + (unsigned)(1024 * (4 * p + w)), halo_off(p, 0));
 #pragma unroll
   for (int s = 0; s < STAGES - 2; ++s) {
     prepare(s);
@@ -219,7 +197,7 @@ __global__ void __launch_bounds__(256, 1) conv_hw_kernel(ConvArgs a) {
   slot_dma(std::integral_constant<int, 0>{}); slot_dma(std::integral_constant<int, 1>{});
   // halo 0 and set 0 landed; set 1 (NAI, tap 1: no halo) and set 2's slots 0..1 (min(NAI, 2) weight pieces:
   // tap 2 has no halo piece) may stay in flight
-  hvm<NAI + (NAI < 2 ? NAI : 2)>();
+  vm_wait<NAI + (NAI < 2 ? NAI : 2)>();
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 
@@ -262,8 +240,8 @@ __global__ void __launch_bounds__(256, 1) conv_hw_kernel(ConvArgs a) {
       if (g == 0) { slot_dma(std::integral_constant<int, 2>{}); slot_dma(std::integral_constant<int, 3>{}); }
       if (g == 1) slot_dma(std::integral_constant<int, 4>{});
     }
-    if (set_has_halo(s + 2)) hvm<NAI + 1>();
-    else hvm<NAI>();
+    if (set_has_halo(s + 2)) vm_wait<NAI + 1>();
+    else vm_wait<NAI>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -314,7 +292,7 @@ __global__ void __launch_bounds__(256, 1) conv_hw_kernel(ConvArgs a) {
 #pragma unroll
     for (int q = STAGES - 1; q >= 1; --q) body(nS - q, T{}, K0{});
   }
-  hvm<0>();
+  vm_wait<0>();
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
@@ -334,18 +312,17 @@ __global__ void __launch_bounds__(256, 1) conv_hw_kernel(ConvArgs a) {
   };
   if constexpr (RES) {
     const int nrec_r = a.M * d.r_cstride * 2;
-    const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(d.residual), (short)0, nrec_r,
-                                                                       0x00020000);
+    const __amdgpu_buffer_rsrc_t rR = buf_rsrc(d.residual, nrec_r);
     constexpr int NRI = 256 / (RPI * 4);
     const int c = lane % CPR;
 #pragma unroll
     for (int k = 0; k < NRI; ++k) {
       const int r = RPI * (w + 4 * k) + lane / CPR;
       const int px = px_of(r);
-      const unsigned off = px >= 0 ? (unsigned)((px * d.r_cstride + d.r_coff + co0 + ((c ^ (r & SWM)) * 8)) * 2) : OOB;
-      dma16h(rR, lds_base + (unsigned)(RPI * (w + 4 * k) * EROWB), off);
+      const unsigned off = px >= 0 ? (unsigned)((px * d.r_cstride + d.r_coff + co0 + ((c ^ (r & SWM)) * 8)) * 2) : kOobOffset;
+      lds_dma16(rR, lds_base + (unsigned)(RPI * (w + 4 * k) * EROWB), off);
     }
-    hvm<0>();
+    vm_wait<0>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
   }

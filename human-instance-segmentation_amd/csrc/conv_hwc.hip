@@ -31,15 +31,6 @@ namespace hiseg {
 #define HISEG_CONV_HWC_MT 3   // work items per multi-tile workgroup (variants 109 / 102)
 #endif
 
-typedef unsigned hc_u4 __attribute__((ext_vector_type(4)));
-typedef unsigned hc_u2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void hc_lds_void;
-
-__device__ __forceinline__ void hc_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned lds_addr, unsigned voff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-               :: "s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff), "s"(rsrc) : "memory");
-}
-
 // ABL (DIAG builds only, timing ablations -- wrong results): bit 0 no weight loads after the prologue, bit 1 no halo
 // DMA after the prologue, bit 2 no B-fragment LDS reads, bit 3 no slice barrier, bit 4 no MFMAs, bit 5 no epilogue
 // (accumulators stored straight, unconverted)
@@ -120,10 +111,8 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
   // ---- XCD-major bijective remap; Cout tiles fastest (the tiles of one pixel block share its halo in L2)
   const int nco = d.Cout_pad / BCO;
   const int ntx = (d.W + TW - 1) / TW, nty = (d.H + 15) >> 4;
-  const int nwg = gridDim.x;
   const int orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7, loc = orig >> 3;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+  const int wg = xcd_major(orig, gridDim.x);
   const int co0 = (wg % nco) * BCO;
   int tl = wg / nco;
   const int tx = tl % ntx;
@@ -132,23 +121,19 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
   const int n = tl / nty;
   const int y0 = ty * 16, x0 = tx * TW;
 
-  const unsigned OOB = 0x80000000u;   // >= num_records: loads return zeros
   const int nsl = a.Cin >> 5;         // 32-channel slices (even: Cin % 64 == 0)
   const int ncb = a.Cin >> 6;
-  const __amdgpu_buffer_rsrc_t rF = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(d.weight_frag), (short)0, d.Cout_pad * 9 * a.Cin * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rF = buf_rsrc(d.weight_frag, d.Cout_pad * 9 * a.Cin * 2);
   constexpr int USH = UP ? 1 : 0;
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(d.srcA), (short)0, d.N * (d.H >> USH) * (d.W >> USH) * d.a_cstride * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(d.Cb ? d.srcB : d.srcA), (short)0, d.Cb ? d.N * d.H * d.W * d.b_cstride * 2 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rA = buf_rsrc(d.srcA, d.N * (d.H >> USH) * (d.W >> USH) * d.a_cstride * 2);
+  const __amdgpu_buffer_rsrc_t rB = buf_rsrc(d.Cb ? d.srcB : d.srcA, d.Cb ? d.N * d.H * d.W * d.b_cstride * 2 : 0);
 
   // ---- A fragments (hiseg.ops.frag_pack): (16-row Cout tile ct, slice sl, tap) at
   // ((((ct * ncb + sl / 2) * 9 + tap) * 2 + sl % 2) * 64 + lane) * 16 B; the wave's two tiles are ct0, ct0 + 1
   const unsigned a_ct = (unsigned)((co0 + wc * 32) >> 4) * (unsigned)ncb * 18u * 1024u;
   const unsigned a_ct_step = (unsigned)ncb * 18u * 1024u;
   // the weights of taps (ky, kx), ky = 0..2, of slice sl: 6 loads (the wave-uniform part in the SGPR offset)
-  auto load_blk = [&](hc_u4 (&af)[3][TM], int sl, int kx) __attribute__((always_inline)) {
+  auto load_blk = [&](u32x4 (&af)[3][TM], int sl, int kx) __attribute__((always_inline)) {
     int ln = lane;
     asm volatile("" : "+v"(ln));
     const unsigned a_lane = a_ct + (unsigned)ln * 16u;
@@ -165,7 +150,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
   // ---- halo layout (conv_hwr's): row hr = hy * 18 + hx (64 B = 32 channels), 16-B chunk c at slot c ^ swz(hx),
   // swz(hx) = 2 ((hx >> 2) & 1); conflict-free B-fragment reads for every column shift kx.  Piece p of wave w = halo
   // rows 16 (NW p + w) + lane / 4 (one LDS-DMA of 1 KiB).
-  const unsigned lds_base = (unsigned)(uintptr_t)(hc_lds_void*)smem;
+  const unsigned lds_base = (unsigned)(uintptr_t)(lds_void*)smem;
   // halo buffer of slice sl (byte offset in LDS)
   auto hbuf = [&](int sl) __attribute__((always_inline)) -> int {
     if constexpr (RP) return ((nsl - 1 - sl) & 1) ? 32 * 1024 : 56 * 1024;
@@ -180,33 +165,33 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
     const int hy = hr / HWD, hx = hr - HWD * hy;
     const int iy = y0 + hy - 1, ix = x0 + hx - 1;
     const bool ok = hr < NHR && (unsigned)iy < (unsigned)d.H && (unsigned)ix < (unsigned)d.W;
-    const int chunk = GA ? (ln & 3) : (ln & 3) ^ (((hx >> 2) & 1) << 1);   // (GA: the swizzle is in the LDS address)
+    const int chunk = GA ? (ln & 3) : (ln & 3) ^ halo_row_swz(hx);   // (GA: the swizzle is in the LDS address)
     const bool fb = 32 * sl >= d.Ca;
     const int cs = fb ? d.b_cstride : d.a_cstride, coff = fb ? d.b_coff + 32 * sl - d.Ca : d.a_coff + 32 * sl;
     if constexpr (UP) {
       const int ush = fb ? 0 : 1;
       return ok ? (unsigned)((((n * (d.H >> ush) + (iy >> ush)) * (d.W >> ush) + (ix >> ush)) * cs + coff + chunk * 8) * 2)
-                : OOB;
+                : kOobOffset;
     } else {
-      return ok ? (unsigned)((((n * d.H + iy) * d.W + ix) * cs + coff + chunk * 8) * 2) : OOB;
+      return ok ? (unsigned)((((n * d.H + iy) * d.W + ix) * cs + coff + chunk * 8) * 2) : kOobOffset;
     }
   };
-  // Each piece's src-A offset at slice 0, computed once: a src-A slice adds 64 B (an out-of-tile lane keeps OOB +
+  // Each piece's src-A offset at slice 0, computed once: a src-A slice adds 64 B (an out-of-tile lane keeps kOobOffset +
   // 64 sl >= 2^31 > num_records).  The per-slice address arithmetic (a division by the halo width, three 32-bit
   // multiplies, the bounds tests: ~30 instructions per piece, issued between two MFMA rows) is gone from the K loop
   // for every src-A slice; src-B slices (the decoder's concatenated skip) keep it.
   unsigned pofA[PPW];
 #pragma unroll
-  for (int p = 0; p < PPW; ++p) pofA[p] = 16 * (NW * p + w) < NHR ? piece_off(p, 0) : OOB;
+  for (int p = 0; p < PPW; ++p) pofA[p] = 16 * (NW * p + w) < NHR ? piece_off(p, 0) : kOobOffset;
   auto halo_dma = [&](int p, int sl, int boff) __attribute__((always_inline)) {
     if (16 * (NW * p + w) >= NHR) return;   // a piece wholly past the halo (wave-uniform): nothing to load
     const bool fb = 32 * sl >= d.Ca;
     const unsigned off = fb ? piece_off(p, sl) : pofA[p] + 64u * (unsigned)sl;
-    hc_dma16(fb ? rB : rA, lds_base + (unsigned)(boff + 1024 * (NW * p + w)), off);
+    lds_dma16(fb ? rB : rA, lds_base + (unsigned)(boff + 1024 * (NW * p + w)), off);
   };
   // GA: piece p's 16 B of slice sl into registers (an out-of-image lane reads zeros: its offset is past num_records)
-  auto halo_ld = [&](int p, int sl) __attribute__((always_inline)) -> hc_u4 {
-    if (16 * (NW * p + w) >= NHR) return hc_u4{0u, 0u, 0u, 0u};
+  auto halo_ld = [&](int p, int sl) __attribute__((always_inline)) -> u32x4 {
+    if (16 * (NW * p + w) >= NHR) return u32x4{0u, 0u, 0u, 0u};
     return __builtin_amdgcn_raw_buffer_load_b128(rA, pofA[p] + 64u * (unsigned)sl, 0, 0);
   };
   // GA: bit p = the slot swizzle of piece p's halo column for this lane
@@ -225,7 +210,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
     g[1] = *reinterpret_cast<const floatx4*>(gate_l + 32 * sl + 4);
   };
   // GA: piece p gated, rounded and written to its place in the halo buffer at boff
-  auto halo_put = [&](int p, int boff, hc_u4 v, const floatx4 (&g)[2]) __attribute__((always_inline)) {
+  auto halo_put = [&](int p, int boff, u32x4 v, const floatx4 (&g)[2]) __attribute__((always_inline)) {
     if (16 * (NW * p + w) >= NHR) return;
     float f[8];
     Chunk<bf16_t>::unpack(__builtin_bit_cast(uint4, v), f);
@@ -239,10 +224,10 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
   };
   const char* lds_c = reinterpret_cast<const char*>(smem);
   // B fragment of halo row r at column shift kx: pixels (r, kx + lane % 16), channels 8 (lane / 16) .. + 7
-  auto rdB = [&](int ln, int boff, int kx, int r) __attribute__((always_inline)) -> hc_u4 {
+  auto rdB = [&](int ln, int boff, int kx, int r) __attribute__((always_inline)) -> u32x4 {
     const int hx = (ln & 15) + kx + 16 * pb;
-    return *reinterpret_cast<const hc_u4*>(lds_c + boff + (r * HWD + hx) * 64 +
-                                           (((ln >> 4) ^ (((hx >> 2) & 1) << 1)) << 4));
+    return *reinterpret_cast<const u32x4*>(lds_c + boff + (r * HWD + hx) * 64 +
+                                           (((ln >> 4) ^ halo_row_swz(hx)) << 4));
   };
 
   floatx4 acc[TM][NR];
@@ -263,16 +248,15 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
     const int y = y0 + r / TW, x = x0 + r % TW;
     return (y < d.Ho && x < d.Wo) ? (n * d.Ho + y) * d.Wo + x : -1;
   };
-  const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(RES ? d.residual : d.out), (short)0, RES ? a.M * d.r_cstride * 2 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rR = buf_rsrc(RES ? d.residual : d.out, RES ? a.M * d.r_cstride * 2 : 0);
   auto res_dma = [&](int k) __attribute__((always_inline)) {
     int ln = lane;
     asm volatile("" : "+v"(ln));
     const int c = ln % CPR;
     const int r = RPI * (w + NW * k) + ln / CPR;
     const int px = px_of(r);
-    const unsigned off = px >= 0 ? (unsigned)((px * d.r_cstride + d.r_coff + co0 + ((c ^ (r & SWM)) * 8)) * 2) : OOB;
-    hc_dma16(rR, lds_base + (unsigned)(RPI * (w + NW * k) * EROWB), off);
+    const unsigned off = px >= 0 ? (unsigned)((px * d.r_cstride + d.r_coff + co0 + ((c ^ (r & SWM)) * 8)) * 2) : kOobOffset;
+    lds_dma16(rR, lds_base + (unsigned)(RPI * (w + NW * k) * EROWB), off);
   };
   static_assert(!RP || (NW == 4 && NRI == 16), "residual prefetch layout: 128-Cout tiles");
 
@@ -293,11 +277,11 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
     }
   }
   // ---- prologue: slice 0's halo, the weights of block (slice 0, kx 0)
-  hc_u4 af[3][TM], an[3][TM];
-  hc_u4 pc[GA ? PH : 1];      // GA: the pieces in flight from one block to the next
+  u32x4 af[3][TM], an[3][TM];
+  u32x4 pc[GA ? PH : 1];      // GA: the pieces in flight from one block to the next
   floatx4 pg[2];              // GA: the gate values for the pieces a block writes
   if constexpr (GA) {         // slices 0 and 1 through registers
-    hc_u4 p0[PPW], p1[PPW];
+    u32x4 p0[PPW], p1[PPW];
     floatx4 g0[2], g1[2];
     gate_ld(g0, 0);
 #pragma unroll
@@ -326,7 +310,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
   load_blk(af, 0, 0);
   if constexpr (GA) {          // (the compiler waits for the pieces where halo_put reads them)
   } else if constexpr (R3) {   // slice 0's pieces (slice 1's, younger, may fly)
-    if (nsl > 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(6 + NPMIN) : "memory");
+    if (nsl > 1) vm_wait<6 + NPMIN>();
     else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
   } else {
     asm volatile("s_waitcnt vmcnt(6)" ::: "memory");    // the halo pieces (older than the 6 weight loads)
@@ -396,7 +380,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
     };
     int ln = lane;
     asm volatile("" : "+v"(ln));
-    hc_u4 bq[3];
+    u32x4 bq[3];
     if constexpr ((ABL & 4) == 0) {
       bq[0] = rdB(ln, buf, KX, 0);
       bq[1] = rdB(ln, buf, KX, 1);
@@ -438,7 +422,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
       } else if constexpr (R3) {
         // slice sl + 1's pieces were issued during slice sl - 1: older than this slice's 18 weight loads and its
         // slice-(sl + 2) pieces, which may fly
-        if (sl + 2 < nsl) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(18 + NPMIN) : "memory");
+        if (sl + 2 < nsl) vm_wait<18 + NPMIN>();
         else if (more) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       } else {
@@ -610,7 +594,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
     const int r = idx / CPR, c = idx % CPR;
     sv[k] = *reinterpret_cast<const uint4*>(tile + r * EROWB + ((c ^ (r & SWM)) << 4));
   }
-  const __amdgpu_buffer_rsrc_t rO = __builtin_amdgcn_make_buffer_rsrc(d.out, (short)0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rO = buf_rsrc(d.out, 0x7fffffff);
 #pragma unroll
   for (int k = 0; k < NST; ++k) {
     const int idx = t + NW * 64 * k;
@@ -618,8 +602,8 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) conv_hwc_kernel(Conv
     const int px = px_of(r), co = co0 + 8 * c;
     const uint4 v = sv[k];
     __builtin_amdgcn_raw_buffer_store_b128(
-        __builtin_bit_cast(hc_u4, v), rO,
-        (px >= 0 && co < d.Cout) ? (unsigned)((px * d.o_cstride + d.o_coff + co) * 2) : OOB, 0, 0);
+        __builtin_bit_cast(u32x4, v), rO,
+        (px >= 0 && co < d.Cout) ? (unsigned)((px * d.o_cstride + d.o_coff + co) * 2) : kOobOffset, 0, 0);
     if constexpr (BR) {
       if (px >= 0 && co < d.Cout) {
         const uint4 zq = zpre[BR ? k : 0];
@@ -762,19 +746,13 @@ __global__ void __launch_bounds__(256, 2) conv_hwc_mt_kernel(ConvArgs a) {
   const int ntx = (d.W + TW - 1) / TW, nty = (d.H + 15) >> 4;
   const int total = d.N * nty * ntx * nco;   // work items
   const int G = gridDim.x;
-  const int orig = blockIdx.x;
-  const int q8 = G >> 3, r8 = G & 7, xcd = orig & 7, loc = orig >> 3;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+  const int wg = xcd_major(blockIdx.x, G);
 
-  const unsigned OOB = 0x80000000u;
   const int nsl = a.Cin >> 5;
   const int ncb = a.Cin >> 6;
-  const __amdgpu_buffer_rsrc_t rF = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(d.weight_frag), (short)0, d.Cout_pad * 9 * a.Cin * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(d.srcA), (short)0, d.N * d.H * d.W * d.a_cstride * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(d.Cb ? d.srcB : d.srcA), (short)0, d.Cb ? d.N * d.H * d.W * d.b_cstride * 2 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rF = buf_rsrc(d.weight_frag, d.Cout_pad * 9 * a.Cin * 2);
+  const __amdgpu_buffer_rsrc_t rA = buf_rsrc(d.srcA, d.N * d.H * d.W * d.a_cstride * 2);
+  const __amdgpu_buffer_rsrc_t rB = buf_rsrc(d.Cb ? d.srcB : d.srcA, d.Cb ? d.N * d.H * d.W * d.b_cstride * 2 : 0);
   const unsigned a_ct_step = (unsigned)ncb * 18u * 1024u;
 
   // tile geometry of work item i (Cout tiles fastest, as conv_hwc_kernel's remap)
@@ -790,7 +768,7 @@ __global__ void __launch_bounds__(256, 2) conv_hwc_mt_kernel(ConvArgs a) {
     g.a_ct = (unsigned)((g.co0 + wc * 32) >> 4) * (unsigned)ncb * 18u * 1024u;
     return g;
   };
-  auto load_blk = [&](hc_u4 (&af)[3][TM], unsigned a_ct, int sl, int kx) __attribute__((always_inline)) {
+  auto load_blk = [&](u32x4 (&af)[3][TM], unsigned a_ct, int sl, int kx) __attribute__((always_inline)) {
     int ln = lane;
     asm volatile("" : "+v"(ln));
     const unsigned a_lane = a_ct + (unsigned)ln * 16u;
@@ -810,34 +788,34 @@ __global__ void __launch_bounds__(256, 2) conv_hwc_mt_kernel(ConvArgs a) {
     const int hy = hr / HWD, hx = hr - HWD * hy;
     const int iy = g.y0 + hy - 1, ix = g.x0 + hx - 1;
     const bool ok = hr < NHR && (unsigned)iy < (unsigned)d.H && (unsigned)ix < (unsigned)d.W;
-    const int chunk = (ln & 3) ^ (((hx >> 2) & 1) << 1);
+    const int chunk = (ln & 3) ^ halo_row_swz(hx);
     const bool fb = 32 * sl >= d.Ca;
     const int cs = fb ? d.b_cstride : d.a_cstride, coff = fb ? d.b_coff + 32 * sl - d.Ca : d.a_coff + 32 * sl;
-    return ok ? (unsigned)((((g.n * d.H + iy) * d.W + ix) * cs + coff + chunk * 8) * 2) : OOB;
+    return ok ? (unsigned)((((g.n * d.H + iy) * d.W + ix) * cs + coff + chunk * 8) * 2) : kOobOffset;
   };
-  const unsigned lds_base = (unsigned)(uintptr_t)(hc_lds_void*)smem;
+  const unsigned lds_base = (unsigned)(uintptr_t)(lds_void*)smem;
   auto hbuf = [&](int sl) __attribute__((always_inline)) -> int { return (sl & 1) * HB; };
   unsigned pofA[PPW];
   auto set_pof = [&](const Geo& g) __attribute__((always_inline)) {
 #pragma unroll
-    for (int p = 0; p < PPW; ++p) pofA[p] = 16 * (NW * p + w) < NHR ? piece_off(g, p, 0) : OOB;
+    for (int p = 0; p < PPW; ++p) pofA[p] = 16 * (NW * p + w) < NHR ? piece_off(g, p, 0) : kOobOffset;
   };
   auto halo_dma = [&](const Geo& g, int p, int sl, int boff) __attribute__((always_inline)) {
     if (16 * (NW * p + w) >= NHR) return;
     const bool fb = 32 * sl >= d.Ca;
     const unsigned off = fb ? piece_off(g, p, sl) : pofA[p] + 64u * (unsigned)sl;
-    hc_dma16(fb ? rB : rA, lds_base + (unsigned)(boff + 1024 * (NW * p + w)), off);
+    lds_dma16(fb ? rB : rA, lds_base + (unsigned)(boff + 1024 * (NW * p + w)), off);
   };
   // the next tile's slice-0 pieces (its offsets computed here, once per tile)
   auto halo_dma0 = [&](const Geo& g, int p) __attribute__((always_inline)) {
     if (16 * (NW * p + w) >= NHR) return;
-    hc_dma16(rA, lds_base + (unsigned)(1024 * (NW * p + w)), piece_off(g, p, 0));
+    lds_dma16(rA, lds_base + (unsigned)(1024 * (NW * p + w)), piece_off(g, p, 0));
   };
   const char* lds_c = reinterpret_cast<const char*>(smem);
-  auto rdB = [&](int ln, int boff, int kx, int r) __attribute__((always_inline)) -> hc_u4 {
+  auto rdB = [&](int ln, int boff, int kx, int r) __attribute__((always_inline)) -> u32x4 {
     const int hx = (ln & 15) + kx + 16 * pb;
-    return *reinterpret_cast<const hc_u4*>(lds_c + boff + (r * HWD + hx) * 64 +
-                                           (((ln >> 4) ^ (((hx >> 2) & 1) << 1)) << 4));
+    return *reinterpret_cast<const u32x4*>(lds_c + boff + (r * HWD + hx) * 64 +
+                                           (((ln >> 4) ^ halo_row_swz(hx)) << 4));
   };
 
   floatx4 acc[TM][NR];
@@ -848,15 +826,14 @@ __global__ void __launch_bounds__(256, 2) conv_hwc_mt_kernel(ConvArgs a) {
   constexpr int NRI = NPX / (RPI * NW);
   static_assert(HALF * EROWB == 32 * 1024 && EOFF + HALF * EROWB <= 80 * 1024 && 2 * HB <= 80 * 1024 && NRI % 2 == 0,
                 "epilogue halves");
-  const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(RES ? d.residual : d.out), (short)0, RES ? a.M * d.r_cstride * 2 : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rO = __builtin_amdgcn_make_buffer_rsrc(d.out, (short)0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rR = buf_rsrc(RES ? d.residual : d.out, RES ? a.M * d.r_cstride * 2 : 0);
+  const __amdgpu_buffer_rsrc_t rO = buf_rsrc(d.out, 0x7fffffff);
   char* E = reinterpret_cast<char*>(smem) + EOFF;
 
   int item = wg;
   Geo g = geo(item);
   set_pof(g);
-  hc_u4 af[3][TM], an[3][TM];
+  u32x4 af[3][TM], an[3][TM];
 #pragma unroll
   for (int p = 0; p < PPW; ++p) halo_dma(g, p, 0, hbuf(0));
   load_blk(af, g.a_ct, 0, 0);
@@ -893,7 +870,7 @@ __global__ void __launch_bounds__(256, 2) conv_hwc_mt_kernel(ConvArgs a) {
       };
       int ln = lane;
       asm volatile("" : "+v"(ln));
-      hc_u4 bq[3];
+      u32x4 bq[3];
       bq[0] = rdB(ln, buf, KX, 0);
       bq[1] = rdB(ln, buf, KX, 1);
       __builtin_amdgcn_s_setprio(1);
@@ -966,8 +943,8 @@ __global__ void __launch_bounds__(256, 2) conv_hwc_mt_kernel(ConvArgs a) {
           const int r = RPI * (w + NW * k) + ln / CPR;
           const int px = px_of(r);
           const unsigned off =
-              px >= 0 ? (unsigned)((px * d.r_cstride + d.r_coff + g.co0 + ((c ^ (r & SWM)) * 8)) * 2) : OOB;
-          hc_dma16(rR, lds_base + (unsigned)(EOFF + (RPI * (w + NW * k) - h * HALF) * EROWB), off);
+              px >= 0 ? (unsigned)((px * d.r_cstride + d.r_coff + g.co0 + ((c ^ (r & SWM)) * 8)) * 2) : kOobOffset;
+          lds_dma16(rR, lds_base + (unsigned)(EOFF + (RPI * (w + NW * k) - h * HALF) * EROWB), off);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -1008,8 +985,8 @@ __global__ void __launch_bounds__(256, 2) conv_hwc_mt_kernel(ConvArgs a) {
         const int r = idx / CPR, c = idx % CPR;
         const int px = px_of(r), co = g.co0 + 8 * c;
         __builtin_amdgcn_raw_buffer_store_b128(
-            __builtin_bit_cast(hc_u4, sv[k]), rO,
-            (px >= 0 && co < d.Cout) ? (unsigned)((px * d.o_cstride + d.o_coff + co) * 2) : OOB, 0, 0);
+            __builtin_bit_cast(u32x4, sv[k]), rO,
+            (px >= 0 && co < d.Cout) ? (unsigned)((px * d.o_cstride + d.o_coff + co) * 2) : kOobOffset, 0, 0);
       }
       // the next tile's first weight block, in flight during the second half (its registers were free)
       if (h == 0 && has_next) load_blk(af, geo(nitem).a_ct, 0, 0);

@@ -20,18 +20,6 @@
 
 namespace hiseg {
 
-typedef unsigned hr_u4 __attribute__((ext_vector_type(4)));
-
-
-__device__ __forceinline__ int hr_hswz(int r) { return ((r >> 2) & 1) << 1; }   // halo rows (any start)
-
-__device__ __forceinline__ void hr_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned lds_addr, unsigned voff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-               :: "s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff), "s"(rsrc) : "memory");
-}
-
-typedef __attribute__((address_space(3))) void hr_lds_void;
-
 // SCH (schedule of a K step): bit 1 -- s_setprio 1 around the MFMA groups (the co-resident workgroup's wave yields
 // its issue slots to them); bit 2 -- B-fragment reuse across ky (below).  Bit 0 is unused (an earlier interleaving
 // of the B reads between the last group's MFMAs measured slower: the variant numbers stay for the A/B record).
@@ -62,10 +50,7 @@ __global__ void __launch_bounds__(WCO * TWB * 128, (WCO * TWB > 2) ? 1 : 2) conv
   // ---- XCD-major bijective remap; Cout tiles fastest (the tiles of one pixel block share its halo in L2)
   const int nco = d.Cout_pad / BCO;
   const int ntx = (d.W + TW - 1) / TW, nty = (d.H + 15) >> 4;
-  const int nwg = gridDim.x;
-  const int orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7, loc = orig >> 3;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+  const int wg = xcd_major(blockIdx.x, gridDim.x);
   const int co0 = (wg % nco) * BCO;
   int tl = wg / nco;
   const int tx = tl % ntx;
@@ -74,16 +59,12 @@ __global__ void __launch_bounds__(WCO * TWB * 128, (WCO * TWB > 2) ? 1 : 2) conv
   const int n = tl / nty;
   const int y0 = ty * 16, x0 = tx * TW;
 
-  const unsigned OOB = 0x80000000u;   // >= num_records: loads return zeros
   const int nsl = a.Cin >> 5;         // 32-channel slices (even: Cin % 64 == 0)
   const int ncb = a.Cin >> 6;
-  const __amdgpu_buffer_rsrc_t rF = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(d.weight_frag), (short)0, d.Cout_pad * 9 * a.Cin * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rF = buf_rsrc(d.weight_frag, d.Cout_pad * 9 * a.Cin * 2);
   constexpr int USH = UP ? 1 : 0;
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(d.srcA), (short)0, d.N * (d.H >> USH) * (d.W >> USH) * d.a_cstride * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(d.Cb ? d.srcB : d.srcA), (short)0, d.Cb ? d.N * d.H * d.W * d.b_cstride * 2 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rA = buf_rsrc(d.srcA, d.N * (d.H >> USH) * (d.W >> USH) * d.a_cstride * 2);
+  const __amdgpu_buffer_rsrc_t rB = buf_rsrc(d.Cb ? d.srcB : d.srcA, d.Cb ? d.N * d.H * d.W * d.b_cstride * 2 : 0);
 
   // ---- A fragments: (Cout tile ct, slice sl, tap) at ((((ct * ncb + sl / 2) * 9 + tap) * 2 + sl % 2) * 64 + lane) * 16 B:
   // the lane / Cout-tile part in 4 VGPRs, the wave-uniform (slice, tap) part as the SGPR offset of the load
@@ -91,7 +72,7 @@ __global__ void __launch_bounds__(WCO * TWB * 128, (WCO * TWB > 2) ? 1 : 2) conv
   // invariants -- with the halo and B-fragment bases below -- push the kernel past 256 registers and spill)
   const unsigned a_ct = (unsigned)((co0 + wco * 64) >> 4) * (unsigned)ncb * 18u * 1024u;
   const unsigned a_ct_step = (unsigned)ncb * 18u * 1024u;
-  auto load_a = [&](hr_u4 (&af)[TM], int sl, int tap) __attribute__((always_inline)) {
+  auto load_a = [&](u32x4 (&af)[TM], int sl, int tap) __attribute__((always_inline)) {
     const unsigned so = __builtin_amdgcn_readfirstlane((((unsigned)(sl >> 1) * 9u + (unsigned)tap) * 2u + (unsigned)(sl & 1)) * 1024u);
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -106,7 +87,7 @@ __global__ void __launch_bounds__(WCO * TWB * 128, (WCO * TWB > 2) ? 1 : 2) conv
   // Halo pieces: piece p (0..5) of wave w = halo rows hr = 16 (4p + w) + lane / 4, one LDS-DMA (1 KiB) each; lane l
   // lands at byte 16 l of the piece = row hr, slot l % 4, so it fetches chunk (l % 4) ^ swz(hr % 18).  Per piece,
   // once: the source pixel (-1 outside the image / past row 324) and that chunk.
-  const unsigned lds_base = (unsigned)(uintptr_t)(hr_lds_void*)smem;
+  const unsigned lds_base = (unsigned)(uintptr_t)(lds_void*)smem;
   auto halo_dma = [&](int p, int sl, int buf) __attribute__((always_inline)) {
     int ln = lane;
     asm volatile("" : "+v"(ln));
@@ -114,29 +95,29 @@ __global__ void __launch_bounds__(WCO * TWB * 128, (WCO * TWB > 2) ? 1 : 2) conv
     const int hy = hr / HWD, hx = hr - HWD * hy;
     const int iy = y0 + hy - 1, ix = x0 + hx - 1;
     const bool ok = hr < NHR && (unsigned)iy < (unsigned)d.H && (unsigned)ix < (unsigned)d.W;
-    const int chunk = (ln & 3) ^ (((hx >> 2) & 1) << 1);
+    const int chunk = (ln & 3) ^ halo_row_swz(hx);
     const bool fb = 32 * sl >= d.Ca;
     const int cs = fb ? d.b_cstride : d.a_cstride, coff = fb ? d.b_coff + 32 * sl - d.Ca : d.a_coff + 32 * sl;
     unsigned off;
     if constexpr (UP) {
       const int ush = fb ? 0 : 1;
       off = ok ? (unsigned)((((n * (d.H >> ush) + (iy >> ush)) * (d.W >> ush) + (ix >> ush)) * cs + coff + chunk * 8) * 2)
-               : OOB;
+               : kOobOffset;
     } else {
-      off = ok ? (unsigned)((((n * d.H + iy) * d.W + ix) * cs + coff + chunk * 8) * 2) : OOB;
+      off = ok ? (unsigned)((((n * d.H + iy) * d.W + ix) * cs + coff + chunk * 8) * 2) : kOobOffset;
     }
-    hr_dma16(fb ? rB : rA, lds_base + (unsigned)(buf * HB + 1024 * (NW * p + w)), off);
+    lds_dma16(fb ? rB : rA, lds_base + (unsigned)(buf * HB + 1024 * (NW * p + w)), off);
   };
   char* lds_c = reinterpret_cast<char*>(smem);
   // B fragment: pixel (tile row wpx*8 + j, column lane % 16) at tap (ky, kx), channels 8 (lane / 16) .. + 7:
   // halo row (wpx * 8 + j + ky, lane % 16 + kx)
   auto bsw = [&](int ln, int kx) __attribute__((always_inline)) -> int {
     const int hx = (ln & 15) + kx + 16 * (wpx >> 1);
-    return ((wpx & 1) * TN * HWD + hx) * 64 + (((ln >> 4) ^ (((hx >> 2) & 1) << 1)) << 4);
+    return ((wpx & 1) * TN * HWD + hx) * 64 + (((ln >> 4) ^ halo_row_swz(hx)) << 4);
   };
-  auto rdB = [&](int ln, int buf, int tap, int j) __attribute__((always_inline)) -> hr_u4 {
+  auto rdB = [&](int ln, int buf, int tap, int j) __attribute__((always_inline)) -> u32x4 {
     const int ky = tap / 3, kx = tap - 3 * (tap / 3);
-    return *reinterpret_cast<const hr_u4*>(lds_c + bsw(ln, kx) + buf * HB + (j + ky) * HWD * 64);
+    return *reinterpret_cast<const u32x4*>(lds_c + bsw(ln, kx) + buf * HB + (j + ky) * HWD * 64);
   };
 
   floatx4 acc[TM][TN];
@@ -147,7 +128,7 @@ __global__ void __launch_bounds__(WCO * TWB * 128, (WCO * TWB > 2) ? 1 : 2) conv
 
   // ---- prologue: slice 0's halo into buffer 0, the first A fragments
   constexpr int NBMAX = TN + 2;
-  hr_u4 af[TM], bf[NBMAX];
+  u32x4 af[TM], bf[NBMAX];
 #pragma unroll
   for (int p = 0; p < PPW; ++p) halo_dma(p, 0, 0);
   load_a(af, 0, 0);
@@ -253,16 +234,15 @@ __global__ void __launch_bounds__(WCO * TWB * 128, (WCO * TWB > 2) ? 1 : 2) conv
   };
   if constexpr (RES) {
     const int nrec_r = a.M * d.r_cstride * 2;
-    const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(d.residual), (short)0, nrec_r,
-                                                                       0x00020000);
+    const __amdgpu_buffer_rsrc_t rR = buf_rsrc(d.residual, nrec_r);
     constexpr int NRI = NPX / (RPI * NW);
     const int c = lane % CPR;
 #pragma unroll
     for (int k = 0; k < NRI; ++k) {
       const int r = RPI * (w + NW * k) + lane / CPR;
       const int px = px_of(r);
-      const unsigned off = px >= 0 ? (unsigned)((px * d.r_cstride + d.r_coff + co0 + ((c ^ (r & SWM)) * 8)) * 2) : OOB;
-      hr_dma16(rR, lds_base + (unsigned)(RPI * (w + NW * k) * EROWB), off);
+      const unsigned off = px >= 0 ? (unsigned)((px * d.r_cstride + d.r_coff + co0 + ((c ^ (r & SWM)) * 8)) * 2) : kOobOffset;
+      lds_dma16(rR, lds_base + (unsigned)(RPI * (w + NW * k) * EROWB), off);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();

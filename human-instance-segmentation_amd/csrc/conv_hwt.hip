@@ -15,14 +15,6 @@
 
 namespace hiseg {
 
-typedef unsigned ht_u4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void ht_lds_void;
-
-__device__ __forceinline__ void ht_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned lds_addr, unsigned voff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-               :: "s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff), "s"(rsrc) : "memory");
-}
-
 template <int ACT, bool RES>
 __global__ void __launch_bounds__(256, 1) conv_hwt_kernel(ConvArgs a) {
   constexpr int BCO = 128, TM = 4, TN = 16, NB = TN + 2;
@@ -42,10 +34,7 @@ __global__ void __launch_bounds__(256, 1) conv_hwt_kernel(ConvArgs a) {
   // ---- XCD-major bijective remap; Cout tiles fastest (the two Cout tiles of a pixel tile share its halo in L2)
   const int nco = d.Cout_pad / BCO;
   const int ntx = (d.W + TW - 1) / TW, nty = (d.H + TH - 1) / TH;
-  const int nwg = gridDim.x;
-  const int orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7, loc = orig >> 3;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+  const int wg = xcd_major(blockIdx.x, gridDim.x);
   const int co0 = (wg % nco) * BCO;
   int tl = wg / nco;
   const int tx = tl % ntx;
@@ -54,15 +43,11 @@ __global__ void __launch_bounds__(256, 1) conv_hwt_kernel(ConvArgs a) {
   const int n = tl / nty;
   const int y0 = ty * TH, x0 = tx * TW;
 
-  const unsigned OOB = 0x80000000u;   // >= num_records: loads return zeros
   const int nsl = a.Cin >> 5;         // 32-channel slices (even: Cin % 64 == 0)
   const int ncb = a.Cin >> 6;
-  const __amdgpu_buffer_rsrc_t rF = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(d.weight_frag), (short)0, d.Cout_pad * 9 * a.Cin * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(d.srcA), (short)0, d.N * d.H * d.W * d.a_cstride * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(d.Cb ? d.srcB : d.srcA), (short)0, d.Cb ? d.N * d.H * d.W * d.b_cstride * 2 : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rF = buf_rsrc(d.weight_frag, d.Cout_pad * 9 * a.Cin * 2);
+  const __amdgpu_buffer_rsrc_t rA = buf_rsrc(d.srcA, d.N * d.H * d.W * d.a_cstride * 2);
+  const __amdgpu_buffer_rsrc_t rB = buf_rsrc(d.Cb ? d.srcB : d.srcA, d.Cb ? d.N * d.H * d.W * d.b_cstride * 2 : 0);
 
   // ---- A fragments (hiseg.ops.frag_pack): (Cout tile ct, slice sl, tap) at
   // ((((ct * ncb + sl / 2) * 9 + tap) * 2 + sl % 2) * 64 + lane) * 16 B; the wave-uniform (slice, tap) part is the SGPR
@@ -73,7 +58,7 @@ __global__ void __launch_bounds__(256, 1) conv_hwt_kernel(ConvArgs a) {
   // ---- halo layout (conv_hwr's): row hr = hy * 18 + hx (64 B = 32 channels), 16-B chunk c at slot
   // c ^ 2 ((hx >> 2) & 1): a B-fragment read (16 consecutive hx of one hy) is conflict-free for every column shift.
   // Piece p of wave w = halo rows 16 (4 p + w) + lane / 4 (one 1 KiB LDS-DMA), lane l -> row hr, slot l % 4.
-  const unsigned lds_base = (unsigned)(uintptr_t)(ht_lds_void*)smem;
+  const unsigned lds_base = (unsigned)(uintptr_t)(lds_void*)smem;
   auto halo_dma = [&](int p, int sl, int buf) __attribute__((always_inline)) {
     int ln = lane;
     asm volatile("" : "+v"(ln));
@@ -81,19 +66,19 @@ __global__ void __launch_bounds__(256, 1) conv_hwt_kernel(ConvArgs a) {
     const int hy = hr / HWD, hx = hr - HWD * hy;
     const int iy = y0 + hy - 1, ix = x0 + hx - 1;
     const bool ok = hr < NHR && (unsigned)iy < (unsigned)d.H && (unsigned)ix < (unsigned)d.W;
-    const int chunk = (ln & 3) ^ (((hx >> 2) & 1) << 1);
+    const int chunk = (ln & 3) ^ halo_row_swz(hx);
     const bool fb = 32 * sl >= d.Ca;
     const int cs = fb ? d.b_cstride : d.a_cstride, coff = fb ? d.b_coff + 32 * sl - d.Ca : d.a_coff + 32 * sl;
-    const unsigned off = ok ? (unsigned)((((n * d.H + iy) * d.W + ix) * cs + coff + chunk * 8) * 2) : OOB;
-    ht_dma16(fb ? rB : rA, lds_base + (unsigned)(buf * HB + 1024 * (NW * p + w)), off);
+    const unsigned off = ok ? (unsigned)((((n * d.H + iy) * d.W + ix) * cs + coff + chunk * 8) * 2) : kOobOffset;
+    lds_dma16(fb ? rB : rA, lds_base + (unsigned)(buf * HB + 1024 * (NW * p + w)), off);
   };
   const char* lds_c = reinterpret_cast<const char*>(smem);
   // B fragment k of column shift kx: pixel row 16 wpx + k (halo row + ky), column lane % 16 + kx, channels
   // 8 (lane / 16) .. + 7
-  auto rdB = [&](int ln, int buf, int kx, int k) __attribute__((always_inline)) -> ht_u4 {
+  auto rdB = [&](int ln, int buf, int kx, int k) __attribute__((always_inline)) -> u32x4 {
     const int hx = (ln & 15) + kx;
-    const int o = (16 * wpx * HWD + hx) * 64 + (((ln >> 4) ^ (((hx >> 2) & 1) << 1)) << 4);
-    return *reinterpret_cast<const ht_u4*>(lds_c + o + buf * HB + k * HWD * 64);
+    const int o = (16 * wpx * HWD + hx) * 64 + (((ln >> 4) ^ halo_row_swz(hx)) << 4);
+    return *reinterpret_cast<const u32x4*>(lds_c + o + buf * HB + k * HWD * 64);
   };
 
   floatx4 acc[TM][TN];
@@ -106,7 +91,7 @@ __global__ void __launch_bounds__(256, 1) conv_hwt_kernel(ConvArgs a) {
   auto a_soff = [&](int sl, int tap) __attribute__((always_inline)) -> unsigned {
     return __builtin_amdgcn_readfirstlane((((unsigned)(sl >> 1) * 9u + (unsigned)tap) * 2u + (unsigned)(sl & 1)) * 1024u);
   };
-  ht_u4 af[2][TM], bf[NB];
+  u32x4 af[2][TM], bf[NB];
 
   // ---- prologue: slice 0's halo into buffer 0, A fragments of steps 0 and 1 (taps 0 and 3)
 #pragma unroll
@@ -208,16 +193,15 @@ __global__ void __launch_bounds__(256, 1) conv_hwt_kernel(ConvArgs a) {
   __syncthreads();   // every wave is done with the halo buffers
   if constexpr (RES) {
     const int nrec_r = a.M * d.r_cstride * 2;
-    const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(d.residual), (short)0, nrec_r,
-                                                                       0x00020000);
+    const __amdgpu_buffer_rsrc_t rR = buf_rsrc(d.residual, nrec_r);
     constexpr int NRI = NPX / (RPI * NW);   // 32 pieces per wave
     const int c = lane % CPR;
 #pragma unroll 8
     for (int k = 0; k < NRI; ++k) {
       const int r = RPI * (w + NW * k) + lane / CPR;
       const int px = px_of(r);
-      const unsigned off = px >= 0 ? (unsigned)((px * d.r_cstride + d.r_coff + co0 + ((c ^ (r & SWM)) * 8)) * 2) : OOB;
-      ht_dma16(rR, lds_base + (unsigned)(RPI * (w + NW * k) * EROWB), off);
+      const unsigned off = px >= 0 ? (unsigned)((px * d.r_cstride + d.r_coff + co0 + ((c ^ (r & SWM)) * 8)) * 2) : kOobOffset;
+      lds_dma16(rR, lds_base + (unsigned)(RPI * (w + NW * k) * EROWB), off);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();

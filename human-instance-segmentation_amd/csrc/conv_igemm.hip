@@ -30,8 +30,6 @@ namespace hiseg {
 // for 36 K blocks: one global round trip per K block on one workgroup per CU).  Each split stores its raw f32
 // tile to the caller's workspace [split][M][Cout_pad]; conv_splitk_reduce_kernel sums the splits in order and
 // applies the epilogue (deterministic; within f32 re-association of the unsplit kernel).
-typedef unsigned ig_u4 __attribute__((ext_vector_type(4)));
-
 // LIN (bf16; 1x1, pad 0, one source, no upsampling; the launcher checks every tensor fits one 2^31-byte buffer
 // resource): a chunk's source pixel and channel never change along the K loop except by whole K blocks, so its
 // activation, gate and weight byte offsets are computed once and each K block's loads are buffer loads at those
@@ -100,12 +98,11 @@ __global__ void __launch_bounds__(256) conv_igemm_kernel(ConvArgs a) {
   const int Cin = a.Cin;
   const int KW = d.KW;
   static_assert(!LIN || sizeof(T) == 2, "LIN: bf16");
-  const unsigned OOB = 0x80000000u;
   unsigned voff_a[LIN ? A_CH : 1], voff_g[LIN ? A_CH : 1], voff_w[LIN ? W_CH : 1];
   __amdgpu_buffer_rsrc_t rsA, rsG, rsW;
   if constexpr (LIN == 2) {
-    rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(d.srcA), (short)0, 0x7fffffff, 0x00020000);
-    rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(d.weight), (short)0, 0x7fffffff, 0x00020000);
+    rsA = buf_rsrc(d.srcA, 0x7fffffff);
+    rsW = buf_rsrc(d.weight, 0x7fffffff);
     const int ci0 = kb0 * BK + c * KCH;
 #pragma unroll
     for (int i = 0; i < A_CH; ++i) {   // voff_a: tap-(0, 0) byte offset (wrapping); voff_g: the row's tap mask
@@ -123,25 +120,24 @@ __global__ void __launch_bounds__(256) conv_igemm_kernel(ConvArgs a) {
 #pragma unroll
     for (int i = 0; i < W_CH; ++i) {
       const int r = (t >> 3) + 32 * i;
-      voff_w[i] = co0 + r < d.Cout_pad ? (unsigned)(((co0 + r) * d.K_pad + ci0) * 2) : OOB;
+      voff_w[i] = co0 + r < d.Cout_pad ? (unsigned)(((co0 + r) * d.K_pad + ci0) * 2) : kOobOffset;
     }
   }
   if constexpr (LIN == 1) {
-    rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(d.srcA), (short)0, 0x7fffffff, 0x00020000);
-    rsG = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.in_scale ? d.in_scale : reinterpret_cast<const float*>(d.srcA)),
-                                            (short)0, 0x7fffffff, 0x00020000);
-    rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(d.weight), (short)0, 0x7fffffff, 0x00020000);
+    rsA = buf_rsrc(d.srcA, 0x7fffffff);
+    rsG = buf_rsrc(d.in_scale ? d.in_scale : reinterpret_cast<const float*>(d.srcA), 0x7fffffff);
+    rsW = buf_rsrc(d.weight, 0x7fffffff);
     const int ci0 = kb0 * BK + c * KCH;
 #pragma unroll
     for (int i = 0; i < A_CH; ++i) {
       const bool ok = rn[i] >= 0 && riy[i] >= 0 && riy[i] < d.H && rix[i] >= 0 && rix[i] < d.W;
-      voff_a[i] = ok ? (unsigned)((((rn[i] * a.Hs + riy[i]) * a.Ws + rix[i]) * d.a_cstride + d.a_coff + ci0) * 2) : OOB;
-      voff_g[i] = ok ? (unsigned)((rn[i] * d.Ca + ci0) * 4) : OOB;
+      voff_a[i] = ok ? (unsigned)((((rn[i] * a.Hs + riy[i]) * a.Ws + rix[i]) * d.a_cstride + d.a_coff + ci0) * 2) : kOobOffset;
+      voff_g[i] = ok ? (unsigned)((rn[i] * d.Ca + ci0) * 4) : kOobOffset;
     }
 #pragma unroll
     for (int i = 0; i < W_CH; ++i) {
       const int r = (t >> 3) + 32 * i;
-      voff_w[i] = co0 + r < d.Cout_pad ? (unsigned)(((co0 + r) * d.K_pad + ci0) * 2) : OOB;
+      voff_w[i] = co0 + r < d.Cout_pad ? (unsigned)(((co0 + r) * d.K_pad + ci0) * 2) : kOobOffset;
     }
   }
 
@@ -165,7 +161,7 @@ __global__ void __launch_bounds__(256) conv_igemm_kernel(ConvArgs a) {
 #pragma unroll
       for (int i = 0; i < A_CH; ++i) {
         const bool ok = kvalid && ((voff_g[i] >> tap) & 1u);
-        ra[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsA, ok ? voff_a[i] + delta : OOB, 0u, 0));
+        ra[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsA, ok ? voff_a[i] + delta : kOobOffset, 0u, 0));
         rgs[i] = false;
       }
 #pragma unroll
@@ -180,12 +176,12 @@ __global__ void __launch_bounds__(256) conv_igemm_kernel(ConvArgs a) {
       const bool kc = kb * BK + c * KCH < Cin;   // chunks past Cin (the last K block's padding) are zeros
 #pragma unroll
       for (int i = 0; i < A_CH; ++i) {
-        const unsigned va = kc ? voff_a[i] : OOB;
+        const unsigned va = kc ? voff_a[i] : kOobOffset;
         ra[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsA, va, so, 0));
         rgs[i] = false;
         if (d.in_scale) {
-          rgs[i] = kc && voff_a[i] != OOB;
-          const unsigned vg = rgs[i] ? voff_g[i] : OOB;
+          rgs[i] = kc && voff_a[i] != kOobOffset;
+          const unsigned vg = rgs[i] ? voff_g[i] : kOobOffset;
 #pragma unroll
           for (int e = 0; e < GREG; ++e)
             rg[i][e] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsG, vg + 16u * e, 2u * so, 0));

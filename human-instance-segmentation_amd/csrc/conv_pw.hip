@@ -39,9 +39,6 @@ namespace hiseg {
 constexpr int kPwBlk = 32;     // pixels per wave block (two 16-pixel MFMA columns)
 constexpr int kPwActRt = -1;   // ACT template value: activation read from the descriptor at run time
 
-typedef unsigned pw_u4 __attribute__((ext_vector_type(4)));
-typedef unsigned pw_u2 __attribute__((ext_vector_type(2)));
-
 // NKS: k-steps of 32 channels held in registers (nks <= NKS of them used); NKS == 9:
 // k-steps 0..7 from source A (Ca == 256), k-step 8 from source B (Cb <= 32 channels, the rest zero).  Every
 // global access is a buffer instruction whose out-of-range lanes (pixel tail, channel tail, the block past
@@ -62,7 +59,6 @@ __global__ void __launch_bounds__(256, 1) conv_pw_kernel(ConvArgs a, int nct, in
   constexpr int CT = 16 * RB;                  // output columns per workgroup tile
   constexpr int ROWC = NKS * 4 + 1;            // LDS row stride in 16-B chunks (one chunk of padding)
   constexpr int NA = NKS == 9 ? 8 : NKS;       // k-steps from source A
-  constexpr unsigned OOB = 0x80000000u;
   extern __shared__ __attribute__((aligned(16))) uint4 smem[];
   const hiseg_conv2d_desc& d = a.d;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -91,15 +87,14 @@ __global__ void __launch_bounds__(256, 1) conv_pw_kernel(ConvArgs a, int nct, in
   const int wch = nks * 4;                     // chunks per row that are used
   const int nchunk = CT * wch;
   {
-    const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<void*>(d.weight), (short)0, (int)((long long)d.Cout_pad * kc * 16), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rW = buf_rsrc(d.weight, (int)((long long)d.Cout_pad * kc * 16));
     for (int i0 = t; i0 < ((abl & 1) ? 0 : nchunk); i0 += 256 * kPwStage) {
-      pw_u4 v[kPwStage];
+      u32x4 v[kPwStage];
 #pragma unroll
       for (int u = 0; u < kPwStage; ++u) {
         const int i = i0 + 256 * u;
         const int r = i / wch, c = i - r * wch;
-        const unsigned off = i < nchunk ? (unsigned)(((c0 + r) * kc + c) * 16) : 0x80000000u;
+        const unsigned off = i < nchunk ? (unsigned)(((c0 + r) * kc + c) * 16) : kOobOffset;
         v[u] = __builtin_amdgcn_raw_buffer_load_b128(rW, off, 0, 0);
       }
 #pragma unroll
@@ -117,15 +112,14 @@ __global__ void __launch_bounds__(256, 1) conv_pw_kernel(ConvArgs a, int nct, in
   }
   if constexpr (INS) {   // the gate table [N][Ca] f32, 16-B aligned, N Ca a multiple of 8: float4 chunks, staged
     const int n4 = d.N * d.Ca / 4;
-    const __amdgpu_buffer_rsrc_t rG = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(d.in_scale), (short)0, (int)(n4 * 16), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rG = buf_rsrc(d.in_scale, (int)(n4 * 16));
     float4* gl4 = reinterpret_cast<float4*>(gl);
     for (int i0 = t; i0 < n4; i0 += 256 * kPwStage) {
-      pw_u4 v[kPwStage];
+      u32x4 v[kPwStage];
 #pragma unroll
       for (int u = 0; u < kPwStage; ++u) {
         const int i = i0 + 256 * u;
-        v[u] = __builtin_amdgcn_raw_buffer_load_b128(rG, i < n4 ? (unsigned)(i * 16) : 0x80000000u, 0, 0);
+        v[u] = __builtin_amdgcn_raw_buffer_load_b128(rG, i < n4 ? (unsigned)(i * 16) : kOobOffset, 0, 0);
       }
 #pragma unroll
       for (int u = 0; u < kPwStage; ++u) {
@@ -140,27 +134,22 @@ __global__ void __launch_bounds__(256, 1) conv_pw_kernel(ConvArgs a, int nct, in
   const int nblk = (M + kPwBlk - 1) / kPwBlk;
   const int g = lane >> 4, pl = lane & 15;
   const long long out_px = (long long)M * (CONVT ? 4 : 1);
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(d.srcA), (short)0, (int)((long long)M * d.a_cstride * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(NKS == 9 ? d.srcB : d.srcA), (short)0, NKS == 9 ? (int)((long long)M * d.b_cstride * 2) : 0,
-      0x00020000);
-  const __amdgpu_buffer_rsrc_t rO = __builtin_amdgcn_make_buffer_rsrc(d.out, (short)0,
-                                                                     (int)(out_px * d.o_cstride * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rA = buf_rsrc(d.srcA, (int)((long long)M * d.a_cstride * 2));
+  const __amdgpu_buffer_rsrc_t rB =
+      buf_rsrc(NKS == 9 ? d.srcB : d.srcA, NKS == 9 ? (int)((long long)M * d.b_cstride * 2) : 0);
+  const __amdgpu_buffer_rsrc_t rO = buf_rsrc(d.out, (int)(out_px * d.o_cstride * 2));
   // the extra epilogue operand (residual or mul), same layout rules as the output
   const void* xp = RES ? d.residual : MUL ? d.mul : d.out;
   const int x_cs = RES ? d.r_cstride : d.m_cstride, x_coff = RES ? d.r_coff : d.m_coff;
-  const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(xp), (short)0, XOP ? (int)(out_px * x_cs * 2) : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rR = buf_rsrc(xp, XOP ? (int)(out_px * x_cs * 2) : 0);
   const bool bch_ok = NKS == 9 && 8 * g < d.Cb;   // this lane's chunk of the source-B k-step holds channels
-  const __amdgpu_buffer_rsrc_t rS = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(PXS ? d.px_scale : d.scale), (short)0, PXS ? (int)((long long)M * 4) : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rS = buf_rsrc(PXS ? d.px_scale : d.scale, PXS ? (int)((long long)M * 4) : 0);
   // the scales of block b's two pixels of this lane (zero past the last pixel, where the fragments are zero too)
   auto load_ps = [&](int b, float (&ps)[2]) __attribute__((always_inline)) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int p = b * kPwBlk + 16 * j + pl;
-      ps[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rS, p < M ? (unsigned)(p * 4) : OOB, 0, 0));
+      ps[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rS, p < M ? (unsigned)(p * 4) : kOobOffset, 0, 0));
     }
   };
 
@@ -174,12 +163,12 @@ __global__ void __launch_bounds__(256, 1) conv_pw_kernel(ConvArgs a, int nct, in
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int p = b * kPwBlk + 16 * j + pl;
-      pw_u4 v;
+      u32x4 v;
       if (ks < NA) {
-        const unsigned off = (p < M && ch_ok) ? (unsigned)((p * d.a_cstride + d.a_coff + 32 * ks + 8 * g) * 2) : OOB;
+        const unsigned off = (p < M && ch_ok) ? (unsigned)((p * d.a_cstride + d.a_coff + 32 * ks + 8 * g) * 2) : kOobOffset;
         v = __builtin_amdgcn_raw_buffer_load_b128(rA, off, 0, 0);
       } else {
-        const unsigned off = (p < M && bch_ok) ? (unsigned)((p * d.b_cstride + d.b_coff + 8 * g) * 2) : OOB;
+        const unsigned off = (p < M && bch_ok) ? (unsigned)((p * d.b_cstride + d.b_coff + 8 * g) * 2) : kOobOffset;
         v = __builtin_amdgcn_raw_buffer_load_b128(rB, off, 0, 0);
       }
       bk[j] = make_uint4(v.x, v.y, v.z, v.w);
@@ -202,7 +191,7 @@ __global__ void __launch_bounds__(256, 1) conv_pw_kernel(ConvArgs a, int nct, in
   };
   auto offset = [&](int j, int i, int cs, int coff) __attribute__((always_inline)) -> unsigned {
     const int col = c0 + 16 * i + 4 * g;
-    if (pbase[j] < 0 || col >= d.Cout) return OOB;
+    if (pbase[j] < 0 || col >= d.Cout) return kOobOffset;
     if constexpr (CONVT) {
       const int C = d.Cout >> 2, q = col / C, co = col - q * C;
       const int op = pbase[j] + (q >> 1) * (2 * d.Wo) + (q & 1);
@@ -271,7 +260,7 @@ __global__ void __launch_bounds__(256, 1) conv_pw_kernel(ConvArgs a, int nct, in
       if (ks < nks) load_ks(nb, ks, bn[ks]);
     if constexpr (PXS) load_ps(nb, psn);
     set_block(b);
-    pw_u2 rv[XOP ? RB : 1][2];
+    u32x2 rv[XOP ? RB : 1][2];
     if constexpr (XOP) {
 #pragma unroll
       for (int i = 0; i < RB; ++i)
@@ -319,7 +308,7 @@ __global__ void __launch_bounds__(256, 1) conv_pw_kernel(ConvArgs a, int nct, in
           v[e] = apply_act(v[e], act);
           if constexpr (MUL) v[e] *= Quad<bf16_t>::get(make_uint2(rv[i][j].x, rv[i][j].y), e);
         }
-        pw_u2 q;
+        u32x2 q;
         q.x = f2bf2(v[0], v[1]);
         q.y = f2bf2(v[2], v[3]);
         if (!(abl & 16)) __builtin_amdgcn_raw_buffer_store_b64(q, rO, offset(j, i, d.o_cstride, d.o_coff), 0, 0);

@@ -36,14 +36,6 @@
 
 namespace hiseg {
 
-typedef unsigned rb_u4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void rb_lds_void;
-
-__device__ __forceinline__ void rb_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned lds_addr, unsigned voff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-               :: "s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff), "s"(rsrc) : "memory");
-}
-
 constexpr int RB_HP = 20;                 // pixel pitch of the input halo and the intermediate
 constexpr int RB_NPI = 26;                // DMA pieces (16 pixels x 64 B) per input plane
 constexpr int RB_PLANE_I = RB_NPI * 1024;   // bytes of an input plane
@@ -62,10 +54,7 @@ __global__ void __launch_bounds__(256, 2) conv_resblock_kernel(hiseg_conv2d_desc
 
   // ---- XCD-major bijective remap (conv_hwc's): the tiles of one image stay on one XCD's L2
   const int ntx = (d1.W + 15) >> 4, nty = (d1.H + 15) >> 4;
-  const int nwg = gridDim.x;
-  const int orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7, loc = orig >> 3;
-  int tl = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+  int tl = xcd_major(blockIdx.x, gridDim.x);
   const int tx = tl % ntx;
   tl /= ntx;
   const int ty = tl % nty;
@@ -73,17 +62,13 @@ __global__ void __launch_bounds__(256, 2) conv_resblock_kernel(hiseg_conv2d_desc
   const int y0 = ty * 16, x0 = tx * 16;
   const int H = d1.H, W = d1.W;
 
-  const unsigned OOB = 0x80000000u;   // >= num_records: loads return zeros, stores are dropped
-  const __amdgpu_buffer_rsrc_t rF1 = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(d1.weight_frag), (short)0, 64 * 9 * 64 * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rF2 = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(d2.weight_frag), (short)0, 64 * 9 * 64 * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(d1.srcA), (short)0, d1.N * H * W * d1.a_cstride * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rF1 = buf_rsrc(d1.weight_frag, 64 * 9 * 64 * 2);
+  const __amdgpu_buffer_rsrc_t rF2 = buf_rsrc(d2.weight_frag, 64 * 9 * 64 * 2);
+  const __amdgpu_buffer_rsrc_t rA = buf_rsrc(d1.srcA, d1.N * H * W * d1.a_cstride * 2);
 
   // ---- A fragments (hiseg.ops.frag_pack, one 64-channel block): (16-row Cout tile ct, slice sl, tap) at
   // (((ct * 9 + tap) * 2 + sl) * 64 + lane) * 16 B; the wave's two tiles are 2 wc, 2 wc + 1
-  auto load_blk = [&](rb_u4 (&af)[3][2], const __amdgpu_buffer_rsrc_t& rF, int sl, int kx) __attribute__((always_inline)) {
+  auto load_blk = [&](u32x4 (&af)[3][2], const __amdgpu_buffer_rsrc_t& rF, int sl, int kx) __attribute__((always_inline)) {
     int ln = lane;
     asm volatile("" : "+v"(ln));
     const unsigned a_lane = (unsigned)(2 * wc) * 18u * 1024u + (unsigned)ln * 16u;
@@ -96,7 +81,7 @@ __global__ void __launch_bounds__(256, 2) conv_resblock_kernel(hiseg_conv2d_desc
     }
   };
 
-  const unsigned lds_base = (unsigned)(uintptr_t)(rb_lds_void*)smem;
+  const unsigned lds_base = (unsigned)(uintptr_t)(lds_void*)smem;
   const char* lds_c = reinterpret_cast<const char*>(smem);
   char* lds_w = reinterpret_cast<char*>(smem);
 
@@ -113,12 +98,12 @@ __global__ void __launch_bounds__(256, 2) conv_resblock_kernel(hiseg_conv2d_desc
     const int hy = p / RB_HP, hx = p - RB_HP * hy;
     const int iy = y0 - 2 + hy, ix = x0 - 2 + hx;
     const bool ok = hy < RB_HP && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
-    const int chunk = (ln & 3) ^ (((p >> 2) & 1) << 1);
+    const int chunk = (ln & 3) ^ halo_row_swz(p);
     const unsigned off =
-        ok ? (unsigned)((((n * H + iy) * W + ix) * d1.a_cstride + d1.a_coff + 32 * sl + chunk * 8) * 2) : OOB;
-    rb_dma16(rA, lds_base + (unsigned)(RB_PLANE_I * sl + 1024 * pc), off);
+        ok ? (unsigned)((((n * H + iy) * W + ix) * d1.a_cstride + d1.a_coff + 32 * sl + chunk * 8) * 2) : kOobOffset;
+    lds_dma16(rA, lds_base + (unsigned)(RB_PLANE_I * sl + 1024 * pc), off);
   }
-  rb_u4 af[3][2], an[3][2];
+  u32x4 af[3][2], an[3][2];
   load_blk(af, rF1, 0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -148,14 +133,14 @@ __global__ void __launch_bounds__(256, 2) conv_resblock_kernel(hiseg_conv2d_desc
 #pragma unroll
       for (int ky = 0; ky < 3; ++ky) {
         const int tt = j + RB_HP * ky + KX;
-        adr[ky] = RB_PLANE_I * sl + (16 * FPW * ph + tt) * 64 + ((cc ^ (((tt >> 2) & 1) << 1)) << 4);
+        adr[ky] = RB_PLANE_I * sl + (16 * FPW * ph + tt) * 64 + ((cc ^ halo_row_swz(tt)) << 4);
       }
-      auto rd = [&](int idx) __attribute__((always_inline)) -> rb_u4 {
+      auto rd = [&](int idx) __attribute__((always_inline)) -> u32x4 {
         const int ky = idx / FPW, k = idx % FPW;
         const int ko = k == FPW - 1 ? klast * 1024 : k * 1024;
-        return *reinterpret_cast<const rb_u4*>(lds_c + adr[ky] + ko);
+        return *reinterpret_cast<const u32x4*>(lds_c + adr[ky] + ko);
       };
-      rb_u4 bq[RA + 1];
+      u32x4 bq[RA + 1];
 #pragma unroll
       for (int r = 0; r < RA; ++r) bq[r] = rd(r);
       __builtin_amdgcn_s_setprio(1);
@@ -218,7 +203,7 @@ __global__ void __launch_bounds__(256, 2) conv_resblock_kernel(hiseg_conv2d_desc
         if (!ok) o = make_uint2(0u, 0u);
         // channels 16 i + 4 c4 .. + 3 of slice wc: chunk 2 i + c4 / 2, its half c4 % 2
         const int ch = 2 * i + (c4 >> 1);
-        *reinterpret_cast<uint2*>(lds_w + RB_PLANE_M * wc + m * 64 + ((ch ^ (((m >> 2) & 1) << 1)) << 4) +
+        *reinterpret_cast<uint2*>(lds_w + RB_PLANE_M * wc + m * 64 + ((ch ^ halo_row_swz(m)) << 4) +
                                   ((c4 & 1) << 3)) = o;
       }
     }
@@ -240,12 +225,12 @@ __global__ void __launch_bounds__(256, 2) conv_resblock_kernel(hiseg_conv2d_desc
       const int j = ln & 15, cc = ln >> 4;
       // B fragment of ring row 8 ph + r at shift KX: ring pixels (8 ph + r) * 20 + KX + j; the slot swizzle is
       // ((r + (KX + j) / 4) & 1) (5 r and 40 ph have the parities of r and 0)
-      const int se = (cc ^ ((((KX + j) >> 2) & 1) << 1)) << 4;
+      const int se = (cc ^ halo_row_swz(KX + j)) << 4;
       const int base = RB_PLANE_M * sl + (NR2 * RB_HP * ph + KX + j) * 64;
-      auto rd = [&](int r) __attribute__((always_inline)) -> rb_u4 {
-        return *reinterpret_cast<const rb_u4*>(lds_c + base + ((r & 1) ? (se ^ 32) : se) + r * RB_HP * 64);
+      auto rd = [&](int r) __attribute__((always_inline)) -> u32x4 {
+        return *reinterpret_cast<const u32x4*>(lds_c + base + ((r & 1) ? (se ^ 32) : se) + r * RB_HP * 64);
       };
-      rb_u4 bq[3];
+      u32x4 bq[3];
       bq[0] = rd(0);
       bq[1] = rd(1);
       __builtin_amdgcn_s_setprio(1);
@@ -293,8 +278,7 @@ __global__ void __launch_bounds__(256, 2) conv_resblock_kernel(hiseg_conv2d_desc
     const int y = y0 + (r >> 4), x = x0 + (r & 15);
     return (y < H && x < W) ? (n * H + y) * W + x : -1;
   };
-  const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(d2.residual), (short)0, d1.N * H * W * d2.r_cstride * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rR = buf_rsrc(d2.residual, d1.N * H * W * d2.r_cstride * 2);
 #pragma unroll
   for (int k = 0; k < NRI; ++k) {
     int ln = lane;
@@ -302,8 +286,8 @@ __global__ void __launch_bounds__(256, 2) conv_resblock_kernel(hiseg_conv2d_desc
     const int c = ln % CPR;
     const int r = RPI * (w + NW * k) + ln / CPR;
     const int px = px_of(r);
-    const unsigned off = px >= 0 ? (unsigned)((px * d2.r_cstride + d2.r_coff + ((c ^ (r & SWM)) * 8)) * 2) : OOB;
-    rb_dma16(rR, lds_base + (unsigned)(RPI * (w + NW * k) * EROWB), off);
+    const unsigned off = px >= 0 ? (unsigned)((px * d2.r_cstride + d2.r_coff + ((c ^ (r & SWM)) * 8)) * 2) : kOobOffset;
+    lds_dma16(rR, lds_base + (unsigned)(RPI * (w + NW * k) * EROWB), off);
   }
   floatx4 sc[2], sh[2];
 #pragma unroll
@@ -344,16 +328,15 @@ __global__ void __launch_bounds__(256, 2) conv_resblock_kernel(hiseg_conv2d_desc
     const int r = idx / CPR, c = idx % CPR;
     sv[k] = *reinterpret_cast<const uint4*>(tile + r * EROWB + ((c ^ (r & SWM)) << 4));
   }
-  // (num_records: the output's own span, so a lane past the tile -- offset OOB -- is dropped by the hardware)
-  const __amdgpu_buffer_rsrc_t rO = __builtin_amdgcn_make_buffer_rsrc(
-      d2.out, (short)0, d1.N * H * W * d2.o_cstride * 2, 0x00020000);
+  // (num_records: the output's own span, so a lane past the tile -- offset kOobOffset -- is dropped by the hardware)
+  const __amdgpu_buffer_rsrc_t rO = buf_rsrc(d2.out, d1.N * H * W * d2.o_cstride * 2);
 #pragma unroll
   for (int k = 0; k < NST; ++k) {
     const int idx = t + NW * 64 * k;
     const int r = idx / CPR, c = idx % CPR;
     const int px = px_of(r);
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(rb_u4, sv[k]), rO,
-                                           px >= 0 ? (unsigned)((px * d2.o_cstride + d2.o_coff + 8 * c) * 2) : OOB, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, sv[k]), rO,
+                                           px >= 0 ? (unsigned)((px * d2.o_cstride + d2.o_coff + 8 * c) * 2) : kOobOffset, 0, 0);
   }
 }
 

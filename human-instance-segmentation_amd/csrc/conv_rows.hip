@@ -41,12 +41,7 @@ struct RowsGeom {
   static constexpr int NJ = (NDMA + 7) / 8;                    // ... per wave (8 waves)
 };
 
-__device__ __forceinline__ void rows_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned lds_addr, unsigned voff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-               :: "s"(lds_addr), "v"(voff), "s"(rsrc) : "memory");
-}
-
-// Two-resource form (sources far apart): the lanes of source A load through rsrc_a, those of source B through
+// Two-resource form of lds_dma16 (sources far apart): the lanes of source A load through rsrc_a, those of source B through
 // rsrc_b, into the same LDS slots -- two instructions under complementary exec masks (both non-empty: mixed groups
 // only; the caller handles single-source groups), exec restored inside the asm block.
 __device__ __forceinline__ void rows_dma16_ab(__amdgpu_buffer_rsrc_t rsrc_a, __amdgpu_buffer_rsrc_t rsrc_b,
@@ -72,7 +67,6 @@ __device__ uint4 g_conv_rows_sink[64];            // the stores of dead lanes / 
 
 template <typename TO>
 __device__ __forceinline__ void rows_store(void* p, const float (&v)[4], bool vec4) {
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
   if constexpr (sizeof(TO) == 2) {
     const u32x2 q = {f2bf2(v[0], v[1]), f2bf2(v[2], v[3])};
     asm volatile("global_store_dwordx2 %0, %1, off" :: "v"(p), "v"(q) : "memory");
@@ -163,11 +157,8 @@ __global__ void __launch_bounds__(512, 2 * OCC) conv_rows_kernel(ConvArgs a, int
   // issues NJ per row; j >= NDMA goes to the sink slots.
   const char* const base = TWO ? reinterpret_cast<const char*>(a.d.srcA)
                                : reinterpret_cast<const char*>(a.d.Cb && a.d.srcB < a.d.srcA ? a.d.srcB : a.d.srcA);
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), (short)0,
-                                                                        0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(TWO ? a.d.srcB : a.d.srcA), (short)0, 0x7fffffff, 0x00020000);
-  const unsigned OOB = 0x80000000u;
+  const __amdgpu_buffer_rsrc_t rsrc = buf_rsrc(base, 0x7fffffff);
+  const __amdgpu_buffer_rsrc_t rsrc_b = buf_rsrc(TWO ? a.d.srcB : a.d.srcA, 0x7fffffff);
   const int up = a.d.a_up == 2 ? 1 : 0;
   int jpix[NJ], jcoff[NJ];
   bool jA[NJ];
@@ -190,7 +181,7 @@ __global__ void __launch_bounds__(512, 2 * OCC) conv_rows_kernel(ConvArgs a, int
     mA[i] = TWO ? __builtin_amdgcn_ballot_w64(jA[i]) : ~0ull;
     mB[i] = TWO ? ~mA[i] : 0ull;
   }
-  const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) void*)ring;
+  const unsigned lds_base = (unsigned)(uintptr_t)(lds_void*)ring;
   const unsigned lds_sink = lds_base + 16u * (unsigned)(RB * ROWS);
   int col_sx = -1;                             // the strip jcol / jok were computed for
   auto set_strip = [&](int sx) {
@@ -210,21 +201,21 @@ __global__ void __launch_bounds__(512, 2 * OCC) conv_rows_kernel(ConvArgs a, int
     const unsigned slotb = lds_base + 16u * (unsigned)(slot * ROWS);
 #pragma unroll
     for (int i = 0; i < NJ; ++i) {
-      const unsigned off = rok && jok[i] ? jcol[i] + (jA[i] ? rowA : rowB) : OOB;
+      const unsigned off = rok && jok[i] ? jcol[i] + (jA[i] ? rowA : rowB) : kOobOffset;
       const bool real = live && w + 8 * i < NDMA;  // (wave-uniform)
       const unsigned dst = real ? slotb + 1024u * (unsigned)(w + 8 * i) : lds_sink;
       if constexpr (TWO) {                     // exactly two counted instructions per group, whatever its sources
         if (mB[i] == 0ull) {
-          rows_dma16(rsrc, dst, off);
-          rows_dma16(rsrc, lds_sink, OOB);
+          lds_dma16(rsrc, dst, off);
+          lds_dma16(rsrc, lds_sink, kOobOffset);
         } else if (mA[i] == 0ull) {
-          rows_dma16(rsrc_b, dst, off);
-          rows_dma16(rsrc, lds_sink, OOB);
+          lds_dma16(rsrc_b, dst, off);
+          lds_dma16(rsrc, lds_sink, kOobOffset);
         } else {
           rows_dma16_ab(rsrc, rsrc_b, dst, off, mA[i], mB[i]);
         }
       } else {
-        rows_dma16(rsrc, dst, off);
+        lds_dma16(rsrc, dst, off);
       }
     }
   };

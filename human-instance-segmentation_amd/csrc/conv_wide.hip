@@ -34,28 +34,14 @@ constexpr bool HISEG_DIAG_ON = true;
 constexpr bool HISEG_DIAG_ON = false;
 #endif
 
-typedef __attribute__((address_space(3))) void lds_void_w;
-
-__device__ __forceinline__ void dma16w(__amdgpu_buffer_rsrc_t rsrc, unsigned lds_addr, unsigned voff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-               :: "s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff), "s"(rsrc) : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wvm() {
-  asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
-}
-
 // wait until at most k stages of NL DMA instructions each are outstanding
 template <int NL>
 __device__ __forceinline__ void wvm_stages(int k) {
-  if (k <= 0) wvm<0>();
-  else if (k == 1) wvm<NL>();
-  else if (k == 2) wvm<2 * NL>();
-  else wvm<3 * NL>();
+  if (k <= 0) vm_wait<0>();
+  else if (k == 1) vm_wait<NL>();
+  else if (k == 2) vm_wait<2 * NL>();
+  else vm_wait<3 * NL>();
 }
-
-__device__ __forceinline__ int wswz(int r) { return (-(r >> 2)) & 3; }
 
 __device__ __forceinline__ unsigned long long wstamp() {
   unsigned long long t;
@@ -90,10 +76,7 @@ __global__ void __launch_bounds__(256, 1) conv_wide_kernel(ConvArgs a) {
 
   // ---- XCD-major bijective remap, Cout tiles fastest (neighbouring pixel tiles share a halo)
   const int nco = d.Cout_pad / BCO;
-  const int nwg = gridDim.x;
-  const int orig = blockIdx.x;
-  const int q = nwg >> 3, r8 = nwg & 7, xcd = orig & 7, loc = orig >> 3;
-  const int wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + loc;
+  const int wg = xcd_major(blockIdx.x, gridDim.x);
   const int co0 = (wg % nco) * BCO;
   const int px0 = (wg / nco) * BPX;
 
@@ -103,7 +86,7 @@ __global__ void __launch_bounds__(256, 1) conv_wide_kernel(ConvArgs a) {
 #pragma unroll
   for (int i = 0; i < NAI; ++i) {
     const int r = 16 * (w + 4 * i) + lrow;
-    woff[i] = ((unsigned)(co0 + r) * (unsigned)d.K_pad + (unsigned)((slot ^ wswz(r)) * 8)) * 2u;
+    woff[i] = ((unsigned)(co0 + r) * (unsigned)d.K_pad + (unsigned)((slot ^ weight_row_swz(r)) * 8)) * 2u;
   }
   // activation rows: input tap origin (piy, pix), pixel index of tap (0,0) and the lane's swizzled chunk
   int piy[NBI], pix[NBI], pidx[NBI], pch[NBI];
@@ -111,7 +94,7 @@ __global__ void __launch_bounds__(256, 1) conv_wide_kernel(ConvArgs a) {
   for (int i = 0; i < NBI; ++i) {
     const int r = 16 * (w + 4 * i) + lrow;
     const int m = px0 + r;
-    pch[i] = (slot ^ wswz(r)) * 8;
+    pch[i] = (slot ^ weight_row_swz(r)) * 8;
     pidx[i] = 0;
     if (m < a.M) {
       const int ox = m % d.Wo;
@@ -130,9 +113,8 @@ __global__ void __launch_bounds__(256, 1) conv_wide_kernel(ConvArgs a) {
   const int nrec_a = d.N * d.H * d.W * d.a_cstride * 2;
   const int nrec_b = d.Cb ? d.N * d.H * d.W * d.b_cstride * 2 : nrec_a;
   const int nrec_r = RES ? a.M * d.r_cstride * 2 : 0;
-  const unsigned OOB = 0x80000000u;  // >= num_records: the DMA returns zeros
   const int nS = d.K_pad >> 5;
-  const unsigned lds_base = (unsigned)(uintptr_t)(lds_void_w*)smem;
+  const unsigned lds_base = (unsigned)(uintptr_t)(lds_void*)smem;
 
   // ---- the stage to be issued next (tap-major K order of the packed weights), advanced without division
   int n_ci = 0, n_kx = 0, n_ky = 0;
@@ -150,7 +132,7 @@ __global__ void __launch_bounds__(256, 1) conv_wide_kernel(ConvArgs a) {
     const int row = 2 * (w + 4 * k) + (lane >> 5);
     const int c = lane & 31;
     const unsigned base = (unsigned)(((px0 + row) * d.r_cstride + d.r_coff + co0 + ((c ^ (row & 15)) * 8)) * 2);
-    return (unsigned)(row + 64 * q) < m_left ? base + (unsigned)q * r_qinc : OOB;
+    return (unsigned)(row + 64 * q) < m_left ? base + (unsigned)q * r_qinc : kOobOffset;
   };
   // pending stage: per-slot LDS destinations, buffer descriptors (slots < NAI / >= NAI) and lane offsets
   unsigned p_sbase = lds_base, p_voff[NL];
@@ -164,7 +146,7 @@ __global__ void __launch_bounds__(256, 1) conv_wide_kernel(ConvArgs a) {
            (unsigned)__builtin_amdgcn_readfirstlane((unsigned)v);
   };
 #pragma unroll
-  for (int k = 0; k < NL; ++k) p_voff[k] = OOB;
+  for (int k = 0; k < NL; ++k) p_voff[k] = kOobOffset;
   // prepare_live: stage s < nS (branch-free, so that its scalar/vector work can interleave with the MFMAs
   // around it); prepare_dead: a stage past the end -- residual quarter s - nS (PREF) or a DMA set that reads
   // nothing (every offset out of range).
@@ -186,7 +168,7 @@ __global__ void __launch_bounds__(256, 1) conv_wide_kernel(ConvArgs a) {
         const int i = k >= NAI ? k - NAI : 0;
         const int iy = piy[i] + n_ky, ix = pix[i] + n_kx;
         const bool ok = (unsigned)iy < (unsigned)d.H && (unsigned)ix < (unsigned)d.W;
-        p_voff[k] = ok ? (unsigned)((pidx[i] + dpix) * cs + cbase + pch[i]) * 2u : OOB;
+        p_voff[k] = ok ? (unsigned)((pidx[i] + dpix) * cs + cbase + pch[i]) * 2u : kOobOffset;
         if constexpr (NOLOAD == 4) p_voff[k] &= 0xffffu;   // diagnostic: every activation read an L2 hit
       }
     }
@@ -219,7 +201,7 @@ __global__ void __launch_bounds__(256, 1) conv_wide_kernel(ConvArgs a) {
     p_sbase = lds_base + (unsigned)((s % STAGES) * STAGE_BYTES);
     const int qd = s - nS;
 #pragma unroll
-    for (int k = 0; k < NL; ++k) p_voff[k] = PREF && qd < 4 ? res_voff(k, qd) : OOB;
+    for (int k = 0; k < NL; ++k) p_voff[k] = PREF && qd < 4 ? res_voff(k, qd) : kOobOffset;
     if constexpr (PREF) {
       p_baseA = uni(d.residual);
       p_baseB = p_baseA;
@@ -234,14 +216,14 @@ __global__ void __launch_bounds__(256, 1) conv_wide_kernel(ConvArgs a) {
     constexpr int k = decltype(kc)::value;
     // NOLOAD (timing diagnostics): 1 = no DMA in the K loop, 2 = no activation DMA, 3 = no weight DMA
     if constexpr (k < NL && NOLOAD != 1 && !(NOLOAD == 2 && k >= NAI) && !(NOLOAD == 3 && k < NAI)) {
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-          reinterpret_cast<void*>(k < NAI ? p_baseA : p_baseB), (short)0, k < NAI ? p_numA : p_numB, 0x00020000);
-      dma16w(rs, p_sbase + (unsigned)(1024 * (w + 4 * k)), p_voff[k]);
+      const __amdgpu_buffer_rsrc_t rs =
+          buf_rsrc(reinterpret_cast<void*>(k < NAI ? p_baseA : p_baseB), k < NAI ? p_numA : p_numB);
+      lds_dma16(rs, p_sbase + (unsigned)(1024 * (w + 4 * k)), p_voff[k]);
     }
   };
 
   // fragment reads: row (16-aligned block base) + lane%16, chunk lane/16 at its swizzled slot
-  const int lane_off = (lane & 15) * 64 + (((lane >> 4) ^ wswz(lane & 15)) << 4);
+  const int lane_off = (lane & 15) * 64 + (((lane >> 4) ^ weight_row_swz(lane & 15)) << 4);
   const char* lds_c = reinterpret_cast<const char*>(smem);
   auto rdA = [&](int s, int i) __attribute__((always_inline)) {
     return *reinterpret_cast<const uint4*>(lds_c + (s % STAGES) * STAGE_BYTES + (wco * TM * 16 + i * 16) * 64 + lane_off);
@@ -268,7 +250,7 @@ __global__ void __launch_bounds__(256, 1) conv_wide_kernel(ConvArgs a) {
   }
   prepare(STAGES - 2);
   slot_dma(std::integral_constant<int, 0>{}); slot_dma(std::integral_constant<int, 1>{});
-  wvm<(STAGES - 3) * NL + 2>();   // stage 0 landed: the younger stages may stay in flight
+  vm_wait<(STAGES - 3) * NL + 2>();   // stage 0 landed: the younger stages may stay in flight
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
 
@@ -309,7 +291,7 @@ __global__ void __launch_bounds__(256, 1) conv_wide_kernel(ConvArgs a) {
       if (g == 1) { slot_dma(std::integral_constant<int, 4>{}); slot_dma(std::integral_constant<int, 5>{}); }
       if (g == 2) { slot_dma(std::integral_constant<int, 6>{}); slot_dma(std::integral_constant<int, 7>{}); }
     }
-    wvm<(STAGES - 3) * NL>();   // stage s+1 landed, stages s+2 .. s+STAGES-2 may stay in flight
+    vm_wait<(STAGES - 3) * NL>();   // stage s+1 landed, stages s+2 .. s+STAGES-2 may stay in flight
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -339,7 +321,7 @@ __global__ void __launch_bounds__(256, 1) conv_wide_kernel(ConvArgs a) {
   slot_dma(std::integral_constant<int, 2>{}); slot_dma(std::integral_constant<int, 3>{});
   slot_dma(std::integral_constant<int, 4>{}); slot_dma(std::integral_constant<int, 5>{});
   slot_dma(std::integral_constant<int, 6>{}); slot_dma(std::integral_constant<int, 7>{});
-  if constexpr (!PREF) wvm<0>();   // the tail's empty DMA sets have landed (PREF: waited for below)
+  if constexpr (!PREF) vm_wait<0>();   // the tail's empty DMA sets have landed (PREF: waited for below)
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
@@ -359,17 +341,17 @@ __global__ void __launch_bounds__(256, 1) conv_wide_kernel(ConvArgs a) {
     if constexpr (PREF) return ((nS + (r >> 6)) % STAGES) * STAGE_BYTES + (r & 63) * EROWB;
     else return r * EROWB;
   };
-  const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(RES ? d.residual : d.out), (short)0, RES ? nrec_r : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rR = buf_rsrc(RES ? d.residual : d.out, RES ? nrec_r : 0);
   if constexpr (PREF && STAGES == 4) {
     // quarter 3 into the last stage's buffer (every wave is past its reads: the barrier above)
 #pragma unroll
     for (int k = 0; k < NL; ++k)
-      dma16w(rR, lds_base + (unsigned)(((nS + 3) % STAGES) * STAGE_BYTES + 2 * (w + 4 * k) * EROWB), res_voff(k, 3));
-    wvm<NL>();   // quarters 0..2 landed (own DMAs)
+      lds_dma16(rR, lds_base + (unsigned)(((nS + 3) % STAGES) * STAGE_BYTES + 2 * (w + 4 * k) * EROWB), res_voff(k, 3));
+    vm_wait<NL>();   // quarters 0..2 landed (own DMAs)
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
   } else if constexpr (PREF) {
-    wvm<0>();    // every quarter was issued under the last K stages
+    vm_wait<0>();    // every quarter was issued under the last K stages
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
   } else if constexpr (RES) {
@@ -379,10 +361,10 @@ __global__ void __launch_bounds__(256, 1) conv_wide_kernel(ConvArgs a) {
     for (int k = 0; k < NRI; ++k) {
       const int r = RPI * (w + 4 * k) + lane / CPR;
       const int px = px0 + r;
-      const unsigned off = px < a.M ? (unsigned)((px * d.r_cstride + d.r_coff + co0 + ((c ^ (r & 15)) * 8)) * 2) : OOB;
-      dma16w(rR, lds_base + (unsigned)(row_base(RPI * (w + 4 * k))), off);
+      const unsigned off = px < a.M ? (unsigned)((px * d.r_cstride + d.r_coff + co0 + ((c ^ (r & 15)) * 8)) * 2) : kOobOffset;
+      lds_dma16(rR, lds_base + (unsigned)(row_base(RPI * (w + 4 * k))), off);
     }
-    wvm<0>();
+    vm_wait<0>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
   }
@@ -420,7 +402,7 @@ __global__ void __launch_bounds__(256, 1) conv_wide_kernel(ConvArgs a) {
     for (int j = 0; j < TN; ++j)
       if (!(PREF && STAGES == 4) || wpx == 0 || j < 4) epi_frag(i, j);
   if constexpr (PREF && STAGES == 4) {
-    wvm<0>();
+    vm_wait<0>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (wpx == 1) {

@@ -16,6 +16,7 @@
 // The sigmoid of the mask logit and the two logs are plain IEEE f32 (expf, a correctly rounded division, logf): where
 // the probability saturates, log(1 - p + 1e-7) depends on the last bit of p, so the fast reciprocal is not used here.
 #include "common.h"
+#include "gfx950_prims.h"
 #include "hiseg_guided_head.h"
 
 #include <math.h>
@@ -78,9 +79,6 @@ __global__ void __launch_bounds__(kT) guided_attn_kernel(hiseg_guided_attn_desc 
   d.gate[p] = a * d.factor[p];
 }
 
-typedef __bf16 g_bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float g_floatx4 __attribute__((ext_vector_type(4)));
-
 // bf16, C = 256: 8 k-steps of 32 channels, 4 row tiles of 16 hidden units.  One wave per SIMD (the 32 A fragments
 // take 128 registers); a wave walks 16-pixel groups.
 __global__ void __launch_bounds__(kT) guided_attn_mfma_kernel(hiseg_guided_attn_desc d) {
@@ -110,15 +108,15 @@ __global__ void __launch_bounds__(kT) guided_attn_mfma_kernel(hiseg_guided_attn_
     uint4 bf[KS];
 #pragma unroll
     for (int s = 0; s < KS; ++s) bf[s] = src[4 * s];
-    g_floatx4 acc[MT];
+    floatx4 acc[MT];
 #pragma unroll
-    for (int t = 0; t < MT; ++t) acc[t] = (g_floatx4){0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < MT; ++t) acc[t] = (floatx4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < KS; ++s)
 #pragma unroll
       for (int t = 0; t < MT; ++t)
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(g_bf16x8_t, af[t][s]),
-                                                         __builtin_bit_cast(g_bf16x8_t, bf[s]), acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, af[t][s]),
+                                                         __builtin_bit_cast(bf16x8_t, bf[s]), acc[t], 0, 0, 0);
     float sum = 0.f;
 #pragma unroll
     for (int t = 0; t < MT; ++t)

@@ -3,6 +3,7 @@
 // (cdna_hip_programming.md Guideline 13) and grid-sized for 256 CUs.
 #include <float.h>
 #include "common.h"
+#include "gfx950_prims.h"
 #include "head2.h"
 
 namespace hiseg {
@@ -493,8 +494,7 @@ __global__ void __launch_bounds__(256) dwconv_q_kernel(const void* in, int H, in
   if (xcd) {
     const int nwg = gridDim.x * gridDim.y * gridDim.z;
     const int orig = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    const int q8 = nwg >> 3, r8 = nwg & 7, xc = orig & 7, loc = orig >> 3;
-    int wg = (xc < r8 ? xc * (q8 + 1) : r8 * (q8 + 1) + (xc - r8) * q8) + loc;
+    int wg = xcd_major(orig, nwg);
     if (xcd == 2) {
       gz = wg % gridDim.z;
       wg /= gridDim.z;
@@ -627,8 +627,7 @@ __global__ void __launch_bounds__(256) dwconv_t_kernel(const void* in, int H, in
   if (xcd) {
     const int nwg = gridDim.x * gridDim.y * gridDim.z;
     const int orig = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    const int q8 = nwg >> 3, r8 = nwg & 7, xc = orig & 7, loc = orig >> 3;
-    int wg = (xc < r8 ? xc * (q8 + 1) : r8 * (q8 + 1) + (xc - r8) * q8) + loc;
+    int wg = xcd_major(orig, nwg);
     if (xcd == 2) {   // channel groups fastest: the groups of one tile share the cache lines a group straddles
       gz = wg % gridDim.z;
       wg /= gridDim.z;

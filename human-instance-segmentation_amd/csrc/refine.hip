@@ -13,6 +13,7 @@
 // All arithmetic is f32 in the reference's operation order (double only inside the fixed-order reductions); the
 // backward has no special case at zero (the sqrt's 0/0 is the reference's NaN).
 #include "common.h"
+#include "gfx950_prims.h"
 #include "hiseg_refine.h"
 
 #include <math.h>
@@ -455,8 +456,8 @@ __global__ void __launch_bounds__(kT) ac_bwd_kernel(const float* __restrict__ pr
 // [tap][tile][lane][8]) and 16 pixels of one tile row as the B operand (lane l reads channels 8 (l >> 4) .. + 7 of
 // pixel l & 15: one 16-B LDS read).  The accumulators of a lane are 8 channels of one pixel: folded BatchNorm +
 // ReLU, the 1x1 (32 -> 3) as 8 products per lane summed over the 4 lane groups with two shuffles, then the blend.
-typedef __bf16 r_bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float r_floatx4 __attribute__((ext_vector_type(4)));
+using hiseg::bf16x8_t;
+using hiseg::floatx4;
 constexpr int kFT = 16, kFX = kFT + 4, kFH = kFT + 2;
 
 __global__ void __launch_bounds__(256) refine_fused_kernel(
@@ -537,15 +538,15 @@ __global__ void __launch_bounds__(256) refine_fused_kernel(
 #pragma unroll 1
   for (int pr = 0; pr < 4; ++pr) {
     const int py = wave * 4 + pr;
-    r_floatx4 acc[2] = {r_floatx4{0.f, 0.f, 0.f, 0.f}, r_floatx4{0.f, 0.f, 0.f, 0.f}};
+    floatx4 acc[2] = {floatx4{0.f, 0.f, 0.f, 0.f}, floatx4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
       const int ky = t / 3, kx = t - 3 * ky;
       const uint4 bf = *reinterpret_cast<const uint4*>(&sh1[(py + ky) * kFH + r + kx][4 * g]);
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt)
-        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(r_bf16x8_t, af[t][mt]),
-                                                          __builtin_bit_cast(r_bf16x8_t, bf), acc[mt], 0, 0, 0);
+        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, af[t][mt]),
+                                                          __builtin_bit_cast(bf16x8_t, bf), acc[mt], 0, 0, 0);
     }
     float rr[3] = {0.f, 0.f, 0.f};
 #pragma unroll

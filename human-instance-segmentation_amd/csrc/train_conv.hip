@@ -255,24 +255,6 @@ __global__ void __launch_bounds__(256) conv_wgrad_kernel(WgradArgs a) {
 // applied on the DMA source side (the DMA writes lane-linear).  Im2col halo and tails cost nothing:
 // an out-of-image tap or a pixel past M gets a voffset beyond the buffer range and the DMA writes 0.
 // STAGES-deep ring with counted vmcnt + raw s_barrier, as conv_fast.
-typedef short v4s_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4s_t lds_v4s_t;
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4u_t lds_v4u_t;
-
-__device__ __forceinline__ unsigned trswz(int row, int ch) {
-  return 256u * (unsigned)row + 16u * (unsigned)(ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-}
-
-__device__ __forceinline__ void wg_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned lds_addr, unsigned voff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-               :: "s"(lds_addr), "v"(voff), "s"(rsrc) : "memory");
-}
-
-__device__ __forceinline__ v4s_t tr_read(unsigned byte_addr) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t*)(uintptr_t)byte_addr);
-}
 
 // INC: stride 1, no upsampled source, no ConvTranspose and Ho x Wo = H x W -- each DMA row's X and dY byte offsets
 // advance by PB pixels' stride per stage, kept in registers (wgrad_wide.hip's SHT 2), instead of the per-stage
@@ -302,9 +284,7 @@ __global__ void __launch_bounds__(256) conv_wgrad_tr_kernel(WgradArgs a) {
   // the same time and share its L2: every tap tile of a split re-reads the same (shifted) activation rows
   // and the same dY rows, which otherwise came from HBM once per tile
   const int nkt = (a.Kg + BK - 1) / BK, nct = (a.Cg + BC - 1) / BC;
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7, loc = orig >> 3;
-  const int wgi = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+  const int wgi = xcd_major(blockIdx.x, gridDim.x);
   const int k0 = (wgi % nkt) * BK, j0 = ((wgi / nkt) % nct) * BC, split = wgi / (nkt * nct);
   const int pb_begin = split * a.blocks_per_split;
   const int nblocks = (a.M + PB - 1) / PB;
@@ -321,13 +301,9 @@ __global__ void __launch_bounds__(256) conv_wgrad_tr_kernel(WgradArgs a) {
   const bool tile_a = d.Cb == 0 || k0 % a.Cin < d.Ca;   // (x_tile_src 1: the K tile's one source)
   const char* const xbase = XR ? pa : a.x_tile_src ? (tile_a ? pa : pb) : (pa < pb ? pa : pb);
   const unsigned dA = a.x_tile_src ? 0u : (unsigned)(pa - xbase), dB = a.x_tile_src ? 0u : (unsigned)(pb - xbase);
-  const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(xbase), (short)0, 0x7fffffff,
-                                                                       0x00020000);
-  const __amdgpu_buffer_rsrc_t rXb = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(pb), (short)0, 0x7fffffff,
-                                                                        0x00020000);
-  const __amdgpu_buffer_rsrc_t rY = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.dy), (short)0, 0x7fffffff,
-                                                                       0x00020000);
-  const unsigned OOB = 0x80000000u;
+  const __amdgpu_buffer_rsrc_t rX = buf_rsrc(xbase, 0x7fffffff);
+  const __amdgpu_buffer_rsrc_t rXb = buf_rsrc(pb, 0x7fffffff);
+  const __amdgpu_buffer_rsrc_t rY = buf_rsrc(a.dy, 0x7fffffff);
 
   // per-lane DMA state: instruction i fills rows 4(w + 4i) .. +3; this lane row (lane >> 4), slot lane & 15
   int xo[4], ky[4], kx[4], yo[4];       // X channel offset (or -1 = zero column), tap; dY column offset (or -1)
@@ -340,7 +316,7 @@ __global__ void __launch_bounds__(256) conv_wgrad_tr_kernel(WgradArgs a) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int r = 4 * (w + 4 * i) + (lane >> 4);
-    const int c = (lane & 15) ^ (((r & 3) << 2) | ((r >> 2) & 3));
+    const int c = (lane & 15) ^ tr_image_chunk_swz(r);
     const int k = k0 + 8 * c;
     const int tap = k / a.Cin;
     const int ci = k - tap * a.Cin;
@@ -380,7 +356,7 @@ __global__ void __launch_bounds__(256) conv_wgrad_tr_kernel(WgradArgs a) {
   }
   const unsigned yb_step = 2u * PB * (unsigned)a.dy_cs;
   const int adv_x = PB % d.Wo, adv_y = PB / d.Wo;
-  const unsigned lds_base = (unsigned)(uintptr_t)(lds_void_t*)smem;
+  const unsigned lds_base = (unsigned)(uintptr_t)(lds_void*)smem;
 
   static_assert(!TOG || (STAGES == 2 && IMG == 16384), "toggled fragment addressing");
   // LDS byte offsets of stage s's X and dY images
@@ -391,10 +367,10 @@ __global__ void __launch_bounds__(256) conv_wgrad_tr_kernel(WgradArgs a) {
   // the X DMA of instruction i (XR: from the lane's source's resource, under that source's lanes)
   auto dma_x = [&](int i, unsigned lds_addr, unsigned voff) __attribute__((always_inline)) {
     if constexpr (XR) {
-      if (b_lanes & (1u << i)) wg_dma16(rXb, lds_addr, voff);
-      else wg_dma16(rX, lds_addr, voff);
+      if (b_lanes & (1u << i)) lds_dma16(rXb, lds_addr, voff);
+      else lds_dma16(rX, lds_addr, voff);
     } else {
-      wg_dma16(rX, lds_addr, voff);
+      lds_dma16(rX, lds_addr, voff);
     }
   };
   auto issue = [&](int s) __attribute__((always_inline)) {
@@ -406,9 +382,9 @@ __global__ void __launch_bounds__(256) conv_wgrad_tr_kernel(WgradArgs a) {
         const int iy = py[i] - d.pad + ky[i];
         const int ix = px[i] - d.pad + kx[i];
         const bool okx = xo[i] >= 0 && pp[i] < a.M && (unsigned)iy < (unsigned)d.H && (unsigned)ix < (unsigned)d.W;
-        dma_x(i, sb + row_base, okx ? ob[i] : OOB);
+        dma_x(i, sb + row_base, okx ? ob[i] : kOobOffset);
         const bool oky = yo[i] >= 0 && pp[i] < a.M;
-        wg_dma16(rY, sby + row_base, oky ? yb[i] + 2u * (unsigned)yo[i] : OOB);
+        lds_dma16(rY, sby + row_base, oky ? yb[i] + 2u * (unsigned)yo[i] : kOobOffset);
         ob[i] += (unsigned)xcs[i] * (2u * PB);
         yb[i] += yb_step;
         pp[i] += PB;
@@ -423,14 +399,14 @@ __global__ void __launch_bounds__(256) conv_wgrad_tr_kernel(WgradArgs a) {
       const bool okx = xo[i] >= 0 && pp[i] < a.M && (unsigned)iy < (unsigned)d.H && (unsigned)ix < (unsigned)d.W;
       const int sh = xsh[i], Hs = d.H >> sh, Ws = d.W >> sh;
       const unsigned offx =
-          okx ? xd[i] + (unsigned)((((pn[i] * Hs + (iy >> sh)) * Ws + (ix >> sh)) * xcs[i] + xo[i]) * 2) : OOB;
+          okx ? xd[i] + (unsigned)((((pn[i] * Hs + (iy >> sh)) * Ws + (ix >> sh)) * xcs[i] + xo[i]) * 2) : kOobOffset;
       dma_x(i, sb + row_base, offx);
       const bool oky = yo[i] >= 0 && pp[i] < a.M;
       int yp = pp[i];
       if (d.convT)   // the dY pixel of sub-pixel q: (n, 2y + q/2, 2x + q%2) of the 2H x 2W output grid
         yp = (pn[i] * (2 * d.Ho) + 2 * py[i] + (yq[i] >> 1)) * (2 * d.Wo) + 2 * px[i] + (yq[i] & 1);
-      const unsigned offy = oky ? (unsigned)((yp * a.dy_cs + yo[i]) * 2) : OOB;
-      wg_dma16(rY, sby + row_base, offy);
+      const unsigned offy = oky ? (unsigned)((yp * a.dy_cs + yo[i]) * 2) : kOobOffset;
+      lds_dma16(rY, sby + row_base, offy);
       // advance this row by PB pixels
       pp[i] += PB;
       px[i] += adv_x;
@@ -457,10 +433,10 @@ __global__ void __launch_bounds__(256) conv_wgrad_tr_kernel(WgradArgs a) {
     for (int hi = 0; hi < 2; ++hi) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
-        oX[i][hi] = lds_base + xoff(0) + trswz(8 * g + q + 4 * hi, (wk * TM * 16 + i * 16) / 8 + (pq >> 1)) + 8u * (pq & 1);
+        oX[i][hi] = lds_base + xoff(0) + tr_image_swz(8 * g + q + 4 * hi, (wk * TM * 16 + i * 16) / 8 + (pq >> 1)) + 8u * (pq & 1);
 #pragma unroll
       for (int j = 0; j < TN; ++j)
-        oY[j][hi] = lds_base + yoff(0) + trswz(8 * g + q + 4 * hi, (wc * TN * 16 + j * 16) / 8 + (pq >> 1)) + 8u * (pq & 1);
+        oY[j][hi] = lds_base + yoff(0) + tr_image_swz(8 * g + q + 4 * hi, (wc * TN * 16 + j * 16) / 8 + (pq >> 1)) + 8u * (pq & 1);
     }
   }
 
@@ -471,8 +447,8 @@ __global__ void __launch_bounds__(256) conv_wgrad_tr_kernel(WgradArgs a) {
   for (int it = 0; it < nit; ++it) {
     if (it + STAGES - 2 < nit) {
       if constexpr (STAGES == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else if constexpr (STAGES == 3) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NL) : "memory");
-      else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * NL) : "memory");
+      else if constexpr (STAGES == 3) vm_wait<NL>();
+      else vm_wait<2 * NL>();
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -482,8 +458,8 @@ __global__ void __launch_bounds__(256) conv_wgrad_tr_kernel(WgradArgs a) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
         if (bias_lanes & (1u << i))
-          *reinterpret_cast<lds_v4u_t*>((uintptr_t)(sb + 256u * (unsigned)(4 * (w + 4 * i)) + 16u * (unsigned)lane)) =
-              v4u_t{0x3f80u, 0u, 0u, 0u};
+          *reinterpret_cast<__attribute__((address_space(3))) u32x4*>(
+              (uintptr_t)(sb + 256u * (unsigned)(4 * (w + 4 * i)) + 16u * (unsigned)lane)) = u32x4{0x3f80u, 0u, 0u, 0u};
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -499,19 +475,19 @@ __global__ void __launch_bounds__(256) conv_wgrad_tr_kernel(WgradArgs a) {
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         const int ch = (wk * TM * 16 + i * 16) / 8 + (pq >> 1);
-        const unsigned lo_a = TOG ? oX[i][0] + (unsigned)(ks * 32 * 256) : sX + trswz(r0, ch) + 8u * (pq & 1);
-        const unsigned hi_a = TOG ? oX[i][1] + (unsigned)(ks * 32 * 256) : sX + trswz(r0 + 4, ch) + 8u * (pq & 1);
-        const v4s_t lo = tr_read(lo_a);
-        const v4s_t hi = tr_read(hi_a);
+        const unsigned lo_a = TOG ? oX[i][0] + (unsigned)(ks * 32 * 256) : sX + tr_image_swz(r0, ch) + 8u * (pq & 1);
+        const unsigned hi_a = TOG ? oX[i][1] + (unsigned)(ks * 32 * 256) : sX + tr_image_swz(r0 + 4, ch) + 8u * (pq & 1);
+        const i16x4 lo = lds_read_tr16(lo_a);
+        const i16x4 hi = lds_read_tr16(hi_a);
         af[i] = __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
       }
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         const int ch = (wc * TN * 16 + j * 16) / 8 + (pq >> 1);
-        const unsigned lo_a = TOG ? oY[j][0] + (unsigned)(ks * 32 * 256) : sY + trswz(r0, ch) + 8u * (pq & 1);
-        const unsigned hi_a = TOG ? oY[j][1] + (unsigned)(ks * 32 * 256) : sY + trswz(r0 + 4, ch) + 8u * (pq & 1);
-        const v4s_t lo = tr_read(lo_a);
-        const v4s_t hi = tr_read(hi_a);
+        const unsigned lo_a = TOG ? oY[j][0] + (unsigned)(ks * 32 * 256) : sY + tr_image_swz(r0, ch) + 8u * (pq & 1);
+        const unsigned hi_a = TOG ? oY[j][1] + (unsigned)(ks * 32 * 256) : sY + tr_image_swz(r0 + 4, ch) + 8u * (pq & 1);
+        const i16x4 lo = lds_read_tr16(lo_a);
+        const i16x4 hi = lds_read_tr16(hi_a);
         bfr[j] = __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
       }
 #pragma unroll

@@ -1,6 +1,7 @@
 // Weight-gradient launch arguments shared by the transposed-read kernels (train_conv.hip, wgrad_wide.hip).
 #pragma once
 #include "conv_common.h"
+#include "gfx950_prims.h"
 
 namespace hiseg {
 

@@ -25,24 +25,8 @@
 
 namespace hiseg {
 
-typedef short wh_v4s_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) wh_v4s_t wh_lds_v4s_t;
-typedef __attribute__((address_space(3))) void wh_lds_void_t;
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef short wh_v8s_t __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void wh_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned lds_addr, unsigned voff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-               :: "s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff), "s"(rsrc) : "memory");
-}
-
-typedef __attribute__((address_space(3))) char wh_lds_char_t;
-__device__ __forceinline__ wh_v4s_t wh_tr(const wh_lds_char_t* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((wh_lds_v4s_t*)p);
-}
-
-__device__ __forceinline__ bf16x8_t wh_cat(wh_v4s_t lo, wh_v4s_t hi) {
-  const wh_v8s_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+__device__ __forceinline__ bf16x8_t wh_cat(i16x4 lo, i16x4 hi) {
+  const i16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return __builtin_bit_cast(bf16x8_t, v);
 }
 
@@ -68,24 +52,20 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_hwc_kernel(WgradArgs a) {
   const int ntx = (d.W + WH_TW - 1) / WH_TW, nty = (d.H + WH_TR - 1) / WH_TR;
   const int NT = d.N * nty * ntx;
   // XCD-major bijective remap: the (Cout, Cin) tiles of one split -- the same pixel tiles -- run on one XCD
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7, loc = orig >> 3;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+  const int orig = blockIdx.x;
+  const int wg = xcd_major(orig, gridDim.x);
   const int tile = wg % (nco * nci), split = wg / (nco * nci);
   const int co0 = (tile % nco) * 64, ci0 = (tile / nco) * 64;
   const int tps = (NT + a.splits - 1) / a.splits;
   const int t0 = split * tps, t1 = t0 + tps < NT ? t0 + tps : NT;
 
-  const unsigned OOB = 0x80000000u;
   // the workgroup's 64 input channels lie in one source (Ca and Cb multiples of 64): source A, or the concat's B
   const bool srcb = ci0 >= d.Ca;
-  const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(srcb ? d.srcB : d.srcA), (short)0, d.N * d.H * d.W * (srcb ? d.b_cstride : d.a_cstride) * 2,
-      0x00020000);
+  const __amdgpu_buffer_rsrc_t rX =
+      buf_rsrc(srcb ? d.srcB : d.srcA, d.N * d.H * d.W * (srcb ? d.b_cstride : d.a_cstride) * 2);
   const int x_cs = srcb ? d.b_cstride : d.a_cstride, x_c0 = srcb ? d.b_coff + ci0 - d.Ca : d.a_coff + ci0;
-  const __amdgpu_buffer_rsrc_t rY = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(a.dy), (short)0, (a.M * a.dy_cs + a.dy_coff + d.Cout) * 2, 0x00020000);
-  const unsigned lds_base = (unsigned)(uintptr_t)(wh_lds_void_t*)smem;
+  const __amdgpu_buffer_rsrc_t rY = buf_rsrc(a.dy, (a.M * a.dy_cs + a.dy_coff + d.Cout) * 2);
+  const unsigned lds_base = (unsigned)(uintptr_t)(lds_void*)smem;
 
   // ---- DMA of pixel tile tt into stage buffer sb: dY rows (16 pieces, 4 per wave), X halo rows (23 pieces)
   auto dma = [&](int tt, int sb) __attribute__((always_inline)) {
@@ -103,8 +83,8 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_hwc_kernel(WgradArgs a) {
       const int y = y0 + (row >> 4), x = x0 + (row & 15);
       const unsigned off = (y < d.H && x < d.W)
                                ? (unsigned)((((n * d.H + y) * d.W + x) * a.dy_cs + a.dy_coff + co0 + 8 * c) * 2)
-                               : OOB;
-      wh_dma16(rY, sbase + (unsigned)(i * 1024), off);
+                               : kOobOffset;
+      lds_dma16(rY, sbase + (unsigned)(i * 1024), off);
     }
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
@@ -116,8 +96,8 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_hwc_kernel(WgradArgs a) {
         const int iy = y0 - 1 + hy, ix = x0 - 1 + hx;
         const bool ok = hp < WH_NHP && (unsigned)iy < (unsigned)d.H && (unsigned)ix < (unsigned)d.W;
         const unsigned off =
-            ok ? (unsigned)((((n * d.H + iy) * d.W + ix) * x_cs + x_c0 + 8 * c) * 2) : OOB;
-        wh_dma16(rX, sbase + (unsigned)(WH_DY_B + i * 1024), off);
+            ok ? (unsigned)((((n * d.H + iy) * d.W + ix) * x_cs + x_c0 + 8 * c) * 2) : kOobOffset;
+        lds_dma16(rX, sbase + (unsigned)(WH_DY_B + i * 1024), off);
       }
     }
   };
@@ -148,23 +128,23 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_hwc_kernel(WgradArgs a) {
 #pragma unroll
   for (int e = 0; e < 16; ++e) accb[e] = 0.f;
   const bool do_bias = BIAS && ci0 == 0 && wci == 0;   // wave-uniform
-  const bf16x8_t ones = __builtin_bit_cast(bf16x8_t, wh_v8s_t{0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80,
+  const bf16x8_t ones = __builtin_bit_cast(bf16x8_t, i16x8{0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80,
                                                              0x3f80, 0x3f80});
 
-  const wh_lds_char_t* lds = (const wh_lds_char_t*)smem;
-  const wh_lds_char_t* pa = lds + a_lane;
-  const wh_lds_char_t* pb[4] = {lds + b_lane[0], lds + b_lane[1], lds + b_lane[2], lds + b_lane[3]};
+  const lds_char* lds = (const lds_char*)smem;
+  const lds_char* pa = lds + a_lane;
+  const lds_char* pb[4] = {lds + b_lane[0], lds + b_lane[1], lds + b_lane[2], lds + b_lane[3]};
   auto compute = [&](int sb) __attribute__((always_inline)) {
     const int so = sb * WH_STAGE;
-    const wh_lds_char_t* qa = pa + so;
-    const wh_lds_char_t* qb[4] = {pb[0] + so, pb[1] + so, pb[2] + so, pb[3] + so};
+    const lds_char* qa = pa + so;
+    const lds_char* qb[4] = {pb[0] + so, pb[1] + so, pb[2] + so, pb[3] + so};
     auto rdA = [&](int r) __attribute__((always_inline)) -> bf16x8_t {
-      const wh_lds_char_t* ad = qa + r * 16 * 128;
-      return wh_cat(wh_tr(ad), wh_tr(ad + 4 * 128));
+      const lds_char* ad = qa + r * 16 * 128;
+      return wh_cat(lds_read_tr16(ad), lds_read_tr16(ad + 4 * 128));
     };
     auto rdB = [&](int hr, int kx) __attribute__((always_inline)) -> bf16x8_t {
-      const wh_lds_char_t* ad = qb[(2 * hr + kx) & 3] + (WH_DY_B + (WH_HWD * hr + kx) * 128);
-      return wh_cat(wh_tr(ad), wh_tr(ad + 4 * 128));
+      const lds_char* ad = qb[(2 * hr + kx) & 3] + (WH_DY_B + (WH_HWD * hr + kx) * 128);
+      return wh_cat(lds_read_tr16(ad), lds_read_tr16(ad + 4 * 128));
     };
     bf16x8_t ar[4], br[2][3];   // A ring of 4: row hr + 1 is read while row hr - 2 still feeds ky = 2
     br[0][0] = rdB(0, 0); br[0][1] = rdB(0, 1); br[0][2] = rdB(0, 2);

@@ -25,25 +25,6 @@
 
 namespace hiseg {
 
-typedef short ww_v4s_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) ww_v4s_t ww_lds_v4s_t;
-typedef __attribute__((address_space(3))) void ww_lds_void_t;
-typedef unsigned ww_v4u_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) ww_v4u_t ww_lds_v4u_t;
-
-__device__ __forceinline__ unsigned ww_swz(int row, int ch) {
-  return 256u * (unsigned)row + 16u * (unsigned)(ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-}
-
-__device__ __forceinline__ void ww_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned lds_addr, unsigned voff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-               :: "s"(lds_addr), "v"(voff), "s"(rsrc) : "memory");
-}
-
-__device__ __forceinline__ ww_v4s_t ww_tr(unsigned byte_addr) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((ww_lds_v4s_t*)(uintptr_t)byte_addr);
-}
-
 // SHT 1: one source and 256-multiple Cin -- both 128-column X images of a K tile lie in the same tap (their channel
 // offsets 128 apart, both valid or both not), so a row block's tap position, bounds and pixel offset are computed
 // once for the two (the per-stage DMA address math was ~60 % of the wave's VALU instructions,
@@ -74,9 +55,7 @@ __global__ void __launch_bounds__(NW * 64, 1) conv_wgrad_wide_kernel(WgradArgs a
   const int wk = w / WCN, wc = w % WCN;
   // XCD-major bijective remap (conv_wgrad_tr_kernel's): the K / C tiles of one pixel split run on one XCD
   const int nkt = (a.Kg + BK - 1) / BK, nct = (a.Cg + BC - 1) / BC;
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7, loc = orig >> 3;
-  const int wgi = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+  const int wgi = xcd_major(blockIdx.x, gridDim.x);
   const int k0 = (wgi % nkt) * BK, j0 = ((wgi / nkt) % nct) * BC, split = wgi / (nkt * nct);
   // blocks_per_split counts 64-pixel blocks (wgrad_geometry); stages of PB pixels
   const int pb_begin = split * a.blocks_per_split * (64 / PB);
@@ -90,11 +69,8 @@ __global__ void __launch_bounds__(NW * 64, 1) conv_wgrad_wide_kernel(WgradArgs a
   const char* const pb = d.Cb ? reinterpret_cast<const char*>(d.srcB) : pa;
   const char* const xbase = pa < pb ? pa : pb;
   const unsigned dA = (unsigned)(pa - xbase), dB = (unsigned)(pb - xbase);
-  const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(xbase), (short)0, 0x7fffffff,
-                                                                       0x00020000);
-  const __amdgpu_buffer_rsrc_t rY = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.dy), (short)0, 0x7fffffff,
-                                                                       0x00020000);
-  const unsigned OOB = 0x80000000u;
+  const __amdgpu_buffer_rsrc_t rX = buf_rsrc(xbase, 0x7fffffff);
+  const __amdgpu_buffer_rsrc_t rY = buf_rsrc(a.dy, 0x7fffffff);
 
   // per-lane DMA state: instruction i of an image fills rows 4(w + 4i) .. +3; this lane row (lane >> 4), slot
   // lane & 15.  Packed to keep the 256-column tile's state in registers: xo = channel offset (-1: zero column),
@@ -105,7 +81,7 @@ __global__ void __launch_bounds__(NW * 64, 1) conv_wgrad_wide_kernel(WgradArgs a
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
     const int r = 4 * (w + NW * i) + (lane >> 4);
-    const int c = (lane & 15) ^ (((r & 3) << 2) | ((r >> 2) & 3));
+    const int c = (lane & 15) ^ tr_image_chunk_swz(r);
 #pragma unroll
     for (int h = 0; h < NXH; ++h) {
       const int k = k0 + 128 * h + 8 * c;
@@ -147,7 +123,7 @@ __global__ void __launch_bounds__(NW * 64, 1) conv_wgrad_wide_kernel(WgradArgs a
   }
   const unsigned ob_step = 2u * PB * (unsigned)d.a_cstride, yb_step = 2u * PB * (unsigned)a.dy_cs;
   const int adv_x = PB % d.Wo, adv_y = PB / d.Wo;
-  const unsigned lds_base = (unsigned)(uintptr_t)(ww_lds_void_t*)smem;
+  const unsigned lds_base = (unsigned)(uintptr_t)(lds_void*)smem;
   static_assert(!TOG || (STAGES == 2 && IMG == 16384 && BPRE && KS == 2), "toggled fragment addressing");
   auto img_off = [&](int s, int m) __attribute__((always_inline)) -> unsigned {
     return TOG ? (unsigned)((m * STAGES + s) * IMG) : (unsigned)(s * STAGE + m * IMG);
@@ -164,8 +140,8 @@ __global__ void __launch_bounds__(NW * 64, 1) conv_wgrad_wide_kernel(WgradArgs a
       const int iy = py[i] - d.pad + (kk & 15);
       const int ix = px[i] - d.pad + ((kk >> 4) & 15);
       const bool ok = xo[0][i] >= 0 && pp[i] < a.M && (unsigned)iy < (unsigned)d.H && (unsigned)ix < (unsigned)d.W;
-      ww_dma16(rX, lds_base + img_off(s, 0) + row_base, ok ? ob[i] : OOB);
-      ww_dma16(rX, lds_base + img_off(s, 1) + row_base, ok ? ob[i] + 256u : OOB);
+      lds_dma16(rX, lds_base + img_off(s, 0) + row_base, ok ? ob[i] : kOobOffset);
+      lds_dma16(rX, lds_base + img_off(s, 1) + row_base, ok ? ob[i] + 256u : kOobOffset);
     } else if ((p & 1) == 0 && SHT == 1) {
       const int kk = xk[0][i];
       const int iy = py[i] * d.stride - d.pad + (kk & 15);
@@ -175,8 +151,8 @@ __global__ void __launch_bounds__(NW * 64, 1) conv_wgrad_wide_kernel(WgradArgs a
       const unsigned pix = (unsigned)(((pn[i] * Hs + (iy >> sh)) * Ws + (ix >> sh)) * d.a_cstride);
 #pragma unroll
       for (int h = 0; h < NXH; ++h) {
-        const unsigned offx = ok && xo[h][i] >= 0 ? dA + (pix + (unsigned)xo[h][i]) * 2u : OOB;
-        ww_dma16(rX, lds_base + img_off(s, h) + row_base, offx);
+        const unsigned offx = ok && xo[h][i] >= 0 ? dA + (pix + (unsigned)xo[h][i]) * 2u : kOobOffset;
+        lds_dma16(rX, lds_base + img_off(s, h) + row_base, offx);
       }
     } else if ((p & 1) == 0) {
 #pragma unroll
@@ -189,8 +165,8 @@ __global__ void __launch_bounds__(NW * 64, 1) conv_wgrad_wide_kernel(WgradArgs a
         const bool fb = (kk >> 9) & 1;
         const unsigned offx = okx ? (fb ? dB : dA) + (unsigned)((((pn[i] * Hs + (iy >> sh)) * Ws + (ix >> sh)) *
                                                                   (fb ? d.b_cstride : d.a_cstride) + xo[h][i]) * 2)
-                                  : OOB;
-        ww_dma16(rX, lds_base + img_off(s, h) + row_base, offx);
+                                  : kOobOffset;
+        lds_dma16(rX, lds_base + img_off(s, h) + row_base, offx);
       }
     } else {
 #pragma unroll
@@ -202,9 +178,9 @@ __global__ void __launch_bounds__(NW * 64, 1) conv_wgrad_wide_kernel(WgradArgs a
           const int qq = (yv >> 28) & 3;
           yp = (pn[i] * (2 * d.Ho) + 2 * py[i] + (qq >> 1)) * (2 * d.Wo) + 2 * px[i] + (qq & 1);
         }
-        unsigned offy = oky ? (unsigned)((yp * a.dy_cs + (yv & 0x0fffffff)) * 2) : OOB;
-        if constexpr (SHT == 2) offy = oky ? yb[i] + 2u * (unsigned)yv : OOB;
-        ww_dma16(rY, lds_base + img_off(s, NXH + hh) + row_base, offy);
+        unsigned offy = oky ? (unsigned)((yp * a.dy_cs + (yv & 0x0fffffff)) * 2) : kOobOffset;
+        if constexpr (SHT == 2) offy = oky ? yb[i] + 2u * (unsigned)yv : kOobOffset;
+        lds_dma16(rY, lds_base + img_off(s, NXH + hh) + row_base, offy);
       }
       if constexpr (SHT == 2) {
         ob[i] += ob_step;
@@ -243,10 +219,10 @@ __global__ void __launch_bounds__(NW * 64, 1) conv_wgrad_wide_kernel(WgradArgs a
     for (int hi = 0; hi < 2; ++hi) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
-        oX[i][hi] = lds_base + img_off(0, wk) + ww_swz(8 * g + q + 4 * hi, 2 * i + (pq >> 1)) + 8u * (pq & 1);
+        oX[i][hi] = lds_base + img_off(0, wk) + tr_image_swz(8 * g + q + 4 * hi, 2 * i + (pq >> 1)) + 8u * (pq & 1);
 #pragma unroll
       for (int j = 0; j < TN; ++j)
-        oY[j][hi] = lds_base + img_off(0, NXH + yimg) + ww_swz(8 * g + q + 4 * hi, ych0 + 2 * j + (pq >> 1)) +
+        oY[j][hi] = lds_base + img_off(0, NXH + yimg) + tr_image_swz(8 * g + q + 4 * hi, ych0 + 2 * j + (pq >> 1)) +
                     8u * (pq & 1);
     }
   }
@@ -256,7 +232,7 @@ __global__ void __launch_bounds__(NW * 64, 1) conv_wgrad_wide_kernel(WgradArgs a
     if (s0 < nit) issue(s0);
   for (int it = 0; it < nit; ++it) {
     const int cur = it % STAGES;
-    if (STAGES > 2 && it + STAGES - 2 < nit) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NLW * (STAGES - 2)) : "memory");
+    if (STAGES > 2 && it + STAGES - 2 < nit) vm_wait<NLW * (STAGES - 2)>();
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (bias_lanes) {   // the GEMM-bias column: X = 1 in every row, written over the landed DMA zeros
 #pragma unroll
@@ -264,9 +240,9 @@ __global__ void __launch_bounds__(NW * 64, 1) conv_wgrad_wide_kernel(WgradArgs a
 #pragma unroll
         for (int i = 0; i < NI; ++i)
           if (bias_lanes & (1u << (NI * h + i)))
-            *reinterpret_cast<ww_lds_v4u_t*>(
+            *reinterpret_cast<__attribute__((address_space(3))) u32x4*>(
                 (uintptr_t)(lds_base + img_off(cur, h) + 256u * (unsigned)(4 * (w + NW * i)) + 16u * (unsigned)lane)) =
-                ww_v4u_t{0x3f80u, 0u, 0u, 0u};
+                u32x4{0x3f80u, 0u, 0u, 0u};
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();   // stage it landed everywhere; every wave left stage it-1's buffer
@@ -281,24 +257,24 @@ __global__ void __launch_bounds__(NW * 64, 1) conv_wgrad_wide_kernel(WgradArgs a
     bf16x8_t af[TM], bfr[TN];
     auto rdA = [&](int ks, int i) __attribute__((always_inline)) -> bf16x8_t {
       if constexpr (TOG) {
-        const ww_v4s_t lo = ww_tr(oX[i][0] + (unsigned)(ks * 32 * 256));
-        const ww_v4s_t hi = ww_tr(oX[i][1] + (unsigned)(ks * 32 * 256));
+        const i16x4 lo = lds_read_tr16(oX[i][0] + (unsigned)(ks * 32 * 256));
+        const i16x4 hi = lds_read_tr16(oX[i][1] + (unsigned)(ks * 32 * 256));
         return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
       }
       const int r0 = ks * 32 + 8 * g + q, ch = 2 * i + (pq >> 1);
-      const ww_v4s_t lo = ww_tr(sX + ww_swz(r0, ch) + 8u * (pq & 1));
-      const ww_v4s_t hi = ww_tr(sX + ww_swz(r0 + 4, ch) + 8u * (pq & 1));
+      const i16x4 lo = lds_read_tr16(sX + tr_image_swz(r0, ch) + 8u * (pq & 1));
+      const i16x4 hi = lds_read_tr16(sX + tr_image_swz(r0 + 4, ch) + 8u * (pq & 1));
       return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
     };
     auto rdB = [&](int ks, int j) __attribute__((always_inline)) -> bf16x8_t {
       if constexpr (TOG) {
-        const ww_v4s_t lo = ww_tr(oY[j][0] + (unsigned)(ks * 32 * 256));
-        const ww_v4s_t hi = ww_tr(oY[j][1] + (unsigned)(ks * 32 * 256));
+        const i16x4 lo = lds_read_tr16(oY[j][0] + (unsigned)(ks * 32 * 256));
+        const i16x4 hi = lds_read_tr16(oY[j][1] + (unsigned)(ks * 32 * 256));
         return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
       }
       const int r0 = ks * 32 + 8 * g + q, ch = ych0 + 2 * j + (pq >> 1);
-      const ww_v4s_t lo = ww_tr(sY + ww_swz(r0, ch) + 8u * (pq & 1));
-      const ww_v4s_t hi = ww_tr(sY + ww_swz(r0 + 4, ch) + 8u * (pq & 1));
+      const i16x4 lo = lds_read_tr16(sY + tr_image_swz(r0, ch) + 8u * (pq & 1));
+      const i16x4 hi = lds_read_tr16(sY + tr_image_swz(r0 + 4, ch) + 8u * (pq & 1));
       return __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
     };
 #pragma unroll

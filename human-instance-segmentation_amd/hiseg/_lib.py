@@ -289,6 +289,8 @@ def _declare(lib):
         "hiseg_version": ([], c_int),
         "hiseg_last_error_string": ([], ctypes.c_char_p),
         "hiseg_built_for_gfx950": ([], c_int),
+        "hiseg_xcd_major": ([c_int, c_int], c_int),
+        "hiseg_xcd_major_fill": ([c_int, c_int, c_int, P], c_int),
         "hiseg_stream_create_cu_mask": ([ctypes.POINTER(ctypes.c_uint), c_int, ctypes.POINTER(c_void_p)], c_int),
         "hiseg_stream_destroy": ([P], c_int),
         "hiseg_comm_load": ([ctypes.c_char_p], c_int),

@@ -54,6 +54,12 @@ int hiseg_debug_fill_lds(unsigned pattern, int rounds, hiseg_stream_t stream);
  * last reset -- `declined`: a kernel refused the layer for its placement (another kernel took it); `far`: a kernel
  * took it through one buffer resource per source.  Either pointer may be NULL; reset != 0 zeroes both after reading. */
 int hiseg_placement_stats(long long* declined, long long* far, int reset);
+/* TEST ONLY, host only (no launch), not part of the product interface: the XCD-major workgroup remap the kernels
+ * apply to their block id -- the remapped id of dispatch id `block` of a grid of `nblocks` (0 <= block < nblocks,
+ * unchecked).  _fill, for tests/test_xcd_remap.py alone (it checks millions of ids; one call per id would take
+ * seconds), writes the remapped ids of blocks first .. first + count - 1 to out[0..count). */
+int hiseg_xcd_major(int block, int nblocks);
+int hiseg_xcd_major_fill(int nblocks, int first, int count, int* out);
 
 /* A HIP stream whose kernels run only on the CUs whose bits are set in mask[0..nwords) (hipExtStreamCreateWithCUMask),
  * for the serving schedule's full-image UNet stream (hiseg.StreamPipelinedExport(cu_mask=...)); destroy with

@@ -77,6 +77,7 @@ def main():
         flops = 2.0 * N * H * W * Cout * Cin * k * k
         res["tflops"] = round(flops / res["wgrad"] / 1e9, 1)
         res["splits"] = sp.value
+        res["path"] = L.wgrad_last_path()   # the kernel that ran (HISEG_WGRAD_HWC=0 / HISEG_WGRAD_WIDE=0 move it)
         res["checksum"] = float(gw.double().abs().sum())
         out[name] = res
         print(name, json.dumps(res), flush=True)
