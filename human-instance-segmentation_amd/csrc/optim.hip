@@ -111,6 +111,22 @@ __global__ void adamw_commit_kernel(int* steps, int parity) {
 
 constexpr int kMaxSeg = 256;
 
+// a * b, a + b, a - b rounded to f32 on their own.  __fmul_rn / __fadd_rn / __fsub_rn are plain operators to the
+// compiler, which fused the lerp's product into the add or subtract that consumes it: m came out one rounding apart
+// from the order the comment in adamw_seg_kernel gives.
+__device__ __forceinline__ float mul_r(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float add_r(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float sub_r(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+
 // Per-segment step counts (hiseg_adamw_step_segmented): the bias corrections of segment s come from its own
 // count; each thread walks its grid-stride indices upwards, so its segment index only advances.
 __global__ void __launch_bounds__(256) adamw_seg_kernel(float* p, float* g, float* m, float* v, long long n, float lr,
@@ -166,15 +182,15 @@ __global__ void __launch_bounds__(256) adamw_seg_kernel(float* p, float* g, floa
     const float step = s_step[sg], sbc2 = s_sbc2[sg];
     float gi = g[i];
     if (clip) { gi *= c; g[i] = gi; }
-    const float pi = __fmul_rn(p[i], decay);
+    const float pi = mul_r(p[i], decay);
     const float m0 = m[i];
-    const float mi = omb1 < 0.5f ? __fadd_rn(m0, __fmul_rn(omb1, __fsub_rn(gi, m0)))
-                                 : __fsub_rn(gi, __fmul_rn(__fsub_rn(gi, m0), __fsub_rn(1.f, omb1)));
-    const float vi = __fadd_rn(__fmul_rn(v[i], b2), __fmul_rn(__fmul_rn(omb2, gi), gi));
+    const float mi = omb1 < 0.5f ? add_r(m0, mul_r(omb1, sub_r(gi, m0)))
+                                 : sub_r(gi, mul_r(sub_r(gi, m0), sub_r(1.f, omb1)));
+    const float vi = add_r(mul_r(v[i], b2), mul_r(mul_r(omb2, gi), gi));
     m[i] = mi;
     v[i] = vi;
-    const float den = __fadd_rn(__fdiv_rn(__fsqrt_rn(vi), sbc2), eps);
-    p[i] = __fadd_rn(pi, __fmul_rn(-step, __fdiv_rn(mi, den)));
+    const float den = add_r(__fdiv_rn(__fsqrt_rn(vi), sbc2), eps);
+    p[i] = add_r(pi, mul_r(-step, __fdiv_rn(mi, den)));
   }
 }
 
