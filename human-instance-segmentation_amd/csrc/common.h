@@ -23,6 +23,16 @@ __device__ __forceinline__ uint32_t f2bf2(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector((hiseg_f32x2_t){lo, hi}, hiseg_bf16x2_t));
 }
 
+// Order-preserving unsigned encoding of an f32 (atomicMax on the encoding is the maximum of the floats): the
+// device-side image maximum of hiseg_image_max_fwd, decoded by every kernel that reads the /255 flag.
+__device__ __forceinline__ unsigned ord_enc(float f) {
+  const unsigned u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ord_dec(unsigned e) {
+  return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e);
+}
+
 template <typename T> struct Elem;
 template <> struct Elem<float> {
   static constexpr int kChunk = 4;  // elements per 16-B chunk

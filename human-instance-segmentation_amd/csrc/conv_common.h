@@ -32,6 +32,7 @@ int conv_rows_try(const ConvArgs& a, hipStream_t s, int variant);
 bool conv_pw_applies(const ConvArgs& a);
 int conv_pw_gate_images(const ConvArgs& a);
 bool conv_rows_form(const ConvArgs& a);
+bool conv_small_raw_applies(const ConvArgs& a);
 int conv_hwc_stats_tiles(const ConvArgs& a);
 int conv_hwc_fused_variant(const ConvArgs& a, bool r3);
 // The fused 64-channel ResidualBlock (conv_resblock.hip): whether the pair of layers has its form; its launch (a

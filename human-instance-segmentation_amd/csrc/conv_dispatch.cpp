@@ -106,13 +106,15 @@ extern "C" int hiseg_conv2d_stats_tiles(const hiseg_conv2d_desc* d) {
   return conv_hwc_stats_tiles(conv_args(*d));
 }
 
-// The fused operands of rounds 7 and 8 -- whether any is set, and in a combination some kernel has: px_scale alone
-// (the pointwise kernel); head2_out, with or without res_gate; a_gate alone (the 3x3 halo kernel).
+// The fused operands of rounds 7, 8 and 10 -- whether any is set, and in a combination some kernel has: px_scale
+// alone (the pointwise kernel); head2_out, with or without res_gate; a_gate alone (the 3x3 halo kernel); raw_src
+// alone (the halo-tiled direct kernel's stem form).
 static bool has_fused_operands(const hiseg_conv2d_desc* d) {
-  return d->px_scale || d->head2_out || d->a_gate || d->res_gate;
+  return d->px_scale || d->head2_out || d->a_gate || d->res_gate || d->raw_src;
 }
 static bool fused_operands_ok(const hiseg_conv2d_desc* d) {
   if (!has_fused_operands(d)) return false;
+  if (d->raw_src) return !d->px_scale && !d->head2_out && !d->a_gate && !d->res_gate;
   if (d->px_scale) return !d->head2_out && !d->a_gate && !d->res_gate;
   if (d->a_gate) return !d->head2_out && !d->res_gate;
   return d->head2_out != nullptr;   // (res_gate rides with head2_out only)
@@ -125,6 +127,15 @@ extern "C" int hiseg_conv2d_fused_ok(const hiseg_conv2d_desc* d) {
   const long long M = (long long)d->N * d->Ho * d->Wo;
   if (M >= (1ll << 31)) return 0;
   const ConvArgs a = conv_args(*d);
+  if (d->raw_src) {
+    // one launch only: the images (12 B per pixel; 16 as the range split of conv_in_ranges counts the 8-channel bf16
+    // view they stand for) and the output under 2 GiB, and none of the epilogue operands the stem does not have
+    const long long lim = (1ll << 31) - (1ll << 20);
+    if (d->residual || d->mul || d->out2 || (long long)d->N * d->H * d->W * 16 > lim ||
+        M * d->o_cstride * 2 > lim)
+      return 0;
+    return conv_small_raw_applies(a) ? 1 : 0;
+  }
   return d->px_scale ? (conv_pw_applies(a) ? 1 : 0) : (conv_hwc_fused_variant(a, hwc_r3_mode()) ? 1 : 0);
 }
 
@@ -283,6 +294,12 @@ static int conv_one_range(const hiseg_conv2d_desc* d, hipStream_t s, int variant
   ConvArgs a = conv_args(*d);
   // The fused operands of round 7 exist in one kernel each, and no other kernel may take the layer and silently
   // ignore them: the caller asks hiseg_conv2d_fused_ok first.
+  if (d->raw_src) {   // the stem on the raw images: conv_small's staging form, a path of its own
+    const int r = conv_small_try(a, s, 0);
+    HISEG_REQUIRE(r != 0, HISEG_ERR_BAD_ARG, "conv2d: no kernel takes this layer with raw_src (hiseg_conv2d_fused_ok)");
+    if (r > 0) conv_note_path(HISEG_CONV_PATH_STEM_RAW, 1);
+    return r < 0 ? r : HISEG_OK;
+  }
   if (has_fused_operands(d)) {
     const ConvCandidate fc = d->px_scale ? ConvCandidate{&kFamilies[F_PW], 90}
                                          : ConvCandidate{&kFamilies[F_HWC], variant ? variant : hwc_r3_mode() ? 108 : 104};
@@ -363,6 +380,7 @@ static int conv_in_ranges(const hiseg_conv2d_desc* d, hipStream_t s, int variant
     if (d->head2_out) c.head2_out = d->head2_out + 2 * n0 * out_px;      // [pixels][2]
     if (d->a_gate) c.a_gate = d->a_gate + (long long)n0 * d->Ca;         // per-image channel gates [N][Ca]
     if (d->res_gate) c.res_gate = d->res_gate + (long long)n0 * d->Cout;   // [N][Cout]
+    if (d->raw_src) c.raw_src = d->raw_src + 3 * n0 * in_px;             // f32 [N][3][H][W]
     const int r = conv_one_range(&c, s, variant);
     if (r) return r;
   }
@@ -373,8 +391,8 @@ static int conv2d_impl(const hiseg_conv2d_desc* d, hiseg_stream_t stream, int va
   HISEG_REQUIRE(d != nullptr, HISEG_ERR_BAD_ARG, "conv2d: null descriptor");
   HISEG_REQUIRE(d->dtype == HISEG_F32 || d->dtype == HISEG_BF16, HISEG_ERR_BAD_DTYPE, "conv2d: dtype %d", d->dtype);
   HISEG_REQUIRE(d->out_dtype == HISEG_F32 || d->out_dtype == HISEG_BF16, HISEG_ERR_BAD_DTYPE, "conv2d: out_dtype %d", d->out_dtype);
-  HISEG_REQUIRE(d->srcA && d->weight && d->scale && d->shift && (d->out || d->head2_out), HISEG_ERR_BAD_ARG,
-                "conv2d: null pointer");
+  HISEG_REQUIRE((d->srcA || d->raw_src) && d->weight && d->scale && d->shift && (d->out || d->head2_out),
+                HISEG_ERR_BAD_ARG, "conv2d: null pointer");
 #ifdef HISEG_DIAG
   const bool fused_variant = variant == 0 || (variant == 148 && d->a_gate);   // (148: the gated form, for timing)
 #else
@@ -383,8 +401,8 @@ static int conv2d_impl(const hiseg_conv2d_desc* d, hiseg_stream_t stream, int va
   HISEG_REQUIRE(!has_fused_operands(d) ||
                     (fused_variant && !d->stats_partial && !d->bnb_partial && fused_operands_ok(d)),
                 HISEG_ERR_BAD_ARG,
-                "conv2d: px_scale / head2_out / a_gate / res_gate go with the automatic choice alone: px_scale or "
-                "a_gate by itself, res_gate only beside head2_out");
+                "conv2d: px_scale / head2_out / a_gate / res_gate / raw_src go with the automatic choice alone: "
+                "px_scale, a_gate or raw_src by itself, res_gate only beside head2_out");
   HISEG_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Ho > 0 && d->Wo > 0, HISEG_ERR_BAD_SHAPE, "conv2d: empty grid");
   HISEG_REQUIRE(d->KH > 0 && d->KW > 0 && d->stride > 0 && d->pad >= 0, HISEG_ERR_BAD_SHAPE, "conv2d: bad window");
   HISEG_REQUIRE(d->a_up == 1 || d->a_up == 2, HISEG_ERR_BAD_SHAPE, "conv2d: a_up must be 1 or 2");

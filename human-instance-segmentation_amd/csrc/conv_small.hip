@@ -38,7 +38,26 @@ __device__ __forceinline__ unsigned long long stamp_small() {
 // ST: stride (2: the EfficientNet stem, halo of (TH-1)*2+KS rows x 129 columns).  NW: waves per workgroup -- 8
 // where the LDS footprint allows one workgroup per CU (wide-K two-source decoder convs: weights + halo > 80 KB),
 // so that each SIMD still has two waves to hide the staging loads' and the fragment reads' latency.
-template <int KS, int TH, typename TO, int NJ, bool STAMP = false, int ST = 1, int NW = 4>
+// One pixel of the raw-image staging form below: hiseg_input_norm_fwd's arithmetic on the three f32 planes' values
+// (x / 255 when the batch maximum is above 1, then (x - mean) / std; every operation rounded on its own, so no
+// contraction whatever code surrounds the call), rounded to bf16 as Elem<bf16_t>::store does, channels 3..7 zero.
+__device__ __forceinline__ uint4 raw_norm_chunk(float r, float g, float b, bool div255, const float (&mean)[3],
+                                                const float (&stdv)[3]) {
+#pragma clang fp contract(off)
+  float v[3] = {r, g, b};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    if (div255) v[c] = __fdiv_rn(v[c], 255.0f);
+    v[c] = __fdiv_rn(__fsub_rn(v[c], mean[c]), stdv[c]);
+  }
+  return make_uint4((uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16), (uint32_t)f2bf(v[2]), 0u, 0u);
+}
+
+// RAW (the EfficientNet stem, hiseg_conv2d_desc.raw_src): the halo is staged from the raw f32 NCHW images -- three
+// plane loads per halo pixel, consecutive lanes on consecutive columns of one image row -- normalised and rounded by
+// raw_norm_chunk into the pixel's one 16-B chunk (Cin == 8); srcA is not read.  Everything after the staging is the
+// same code on the same LDS contents, so the output has the bits of hiseg_input_norm_fwd + this kernel.
+template <int KS, int TH, typename TO, int NJ, bool STAMP = false, int ST = 1, int NW = 4, bool RAW = false>
 __global__ void __launch_bounds__(NW * 64) conv_small_kernel(ConvArgs a, int WS, int PS) {
   constexpr int NT = NW * 64;
   unsigned long long st0 = 0, st1 = 0, st2 = 0;
@@ -89,33 +108,63 @@ __global__ void __launch_bounds__(NW * 64) conv_small_kernel(ConvArgs a, int WS,
     }
   }
   const int nh = HR * HC * cch;
-  const uint16_t* srcA = reinterpret_cast<const uint16_t*>(d.srcA);
-  const uint16_t* srcB = reinterpret_cast<const uint16_t*>(d.Cb ? d.srcB : d.srcA);
-  for (int i0 = t; i0 < nh; i0 += NT * UB) {
-    uint4 v[UB];
-    bool ok[UB];
+  if constexpr (RAW) {
+    constexpr int NP = HR * HC;   // halo pixels, one chunk each
+    constexpr int UR = (NP + NT - 1) / NT < 10 ? (NP + NT - 1) / NT : 10;   // pixels per thread in flight, 3 loads each
+    const bool div255 = ord_dec(*reinterpret_cast<const unsigned*>(d.raw_max)) > 1.0f;
+    const float mean[3] = {d.raw_mean[0], d.raw_mean[1], d.raw_mean[2]};
+    const float stdv[3] = {d.raw_std[0], d.raw_std[1], d.raw_std[2]};
+    const long long plane = (long long)d.H * d.W;
+    const float* img = d.raw_src + (long long)n * 3 * plane;
+    for (int i0 = t; i0 < NP; i0 += NT * UR) {
+      float v[UR][3];
+      bool ok[UR];
 #pragma unroll
-    for (int u = 0; u < UB; ++u) {
-      const int i = i0 + u * NT;
-      const int pix = dcch.div(i), c = i - pix * cch;
-      const int prow = pix / HC, pcol = pix - prow * HC;
-      const int iy = y0 * ST + prow - pad, ix = x0 * ST + pcol - pad;
-      ok[u] = i < nh && iy >= 0 && iy < d.H && ix >= 0 && ix < d.W;
-      const int ciy = ok[u] ? iy : 0, cix = ok[u] ? ix : 0;
-      const int ci = c * 8;
-      const bool fromA = ci < d.Ca;
-      const int sy = d.a_up == 2 ? (ciy >> 1) : ciy;
-      const int sx = d.a_up == 2 ? (cix >> 1) : cix;
-      const long long offA = (((long long)n * a.Hs + sy) * a.Ws + sx) * d.a_cstride + d.a_coff + ci;
-      const long long offB = (((long long)n * d.H + ciy) * d.W + cix) * d.b_cstride + d.b_coff + (ci - d.Ca);
-      v[u] = *reinterpret_cast<const uint4*>(fromA ? srcA + offA : srcB + offB);
+      for (int u = 0; u < UR; ++u) {
+        const int i = i0 + u * NT;
+        const int prow = i / HC, pcol = i - prow * HC;
+        const int iy = y0 * ST + prow - pad, ix = x0 * ST + pcol - pad;
+        ok[u] = i < NP && iy >= 0 && iy < d.H && ix >= 0 && ix < d.W;
+        const long long off = ok[u] ? (long long)iy * d.W + ix : 0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[u][c] = img[c * plane + off];
+      }
+#pragma unroll
+      for (int u = 0; u < UR; ++u) {
+        const int i = i0 + u * NT;
+        if (i < NP)
+          sX[i * PS] = ok[u] ? raw_norm_chunk(v[u][0], v[u][1], v[u][2], div255, mean, stdv) : make_uint4(0u, 0u, 0u, 0u);
+      }
     }
+  } else {
+    const uint16_t* srcA = reinterpret_cast<const uint16_t*>(d.srcA);
+    const uint16_t* srcB = reinterpret_cast<const uint16_t*>(d.Cb ? d.srcB : d.srcA);
+    for (int i0 = t; i0 < nh; i0 += NT * UB) {
+      uint4 v[UB];
+      bool ok[UB];
 #pragma unroll
-    for (int u = 0; u < UB; ++u) {
-      const int i = i0 + u * NT;
-      if (i < nh) {
+      for (int u = 0; u < UB; ++u) {
+        const int i = i0 + u * NT;
         const int pix = dcch.div(i), c = i - pix * cch;
-        sX[pix * PS + c] = ok[u] ? v[u] : make_uint4(0u, 0u, 0u, 0u);
+        const int prow = pix / HC, pcol = pix - prow * HC;
+        const int iy = y0 * ST + prow - pad, ix = x0 * ST + pcol - pad;
+        ok[u] = i < nh && iy >= 0 && iy < d.H && ix >= 0 && ix < d.W;
+        const int ciy = ok[u] ? iy : 0, cix = ok[u] ? ix : 0;
+        const int ci = c * 8;
+        const bool fromA = ci < d.Ca;
+        const int sy = d.a_up == 2 ? (ciy >> 1) : ciy;
+        const int sx = d.a_up == 2 ? (cix >> 1) : cix;
+        const long long offA = (((long long)n * a.Hs + sy) * a.Ws + sx) * d.a_cstride + d.a_coff + ci;
+        const long long offB = (((long long)n * d.H + ciy) * d.W + cix) * d.b_cstride + d.b_coff + (ci - d.Ca);
+        v[u] = *reinterpret_cast<const uint4*>(fromA ? srcA + offA : srcB + offB);
+      }
+#pragma unroll
+      for (int u = 0; u < UB; ++u) {
+        const int i = i0 + u * NT;
+        if (i < nh) {
+          const int pix = dcch.div(i), c = i - pix * cch;
+          sX[pix * PS + c] = ok[u] ? v[u] : make_uint4(0u, 0u, 0u, 0u);
+        }
       }
     }
   }
@@ -267,11 +316,11 @@ __global__ void __launch_bounds__(NW * 64) conv_small_kernel(ConvArgs a, int WS,
 
 static int odd_slots(int n) { return (n & 1) ? n : n + 1; }
 
-template <int KS, int TH, typename TO, int NJ, bool STAMP, int ST = 1, int NW = 4>
+template <int KS, int TH, typename TO, int NJ, bool STAMP, int ST = 1, int NW = 4, bool RAW = false>
 static int launch_small_nj(const ConvArgs& a, hipStream_t s, int WS, int PS, size_t lds) {
   const hiseg_conv2d_desc& d = a.d;
   const int ntx = (d.Wo + 63) / 64, nty = (d.Ho + TH - 1) / TH;
-  auto kern = conv_small_kernel<KS, TH, TO, NJ, STAMP, ST, NW>;
+  auto kern = conv_small_kernel<KS, TH, TO, NJ, STAMP, ST, NW, RAW>;
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -306,7 +355,12 @@ static int launch_small_s2(const ConvArgs& a, hipStream_t s, int WS, int PS) {
   auto lds_for = [&](int th) { return wbytes + (size_t)((th - 1) * 2 + 3) * (63 * 2 + 3) * PS * 16; };
   const int nco = d.Cout_pad / 16;
   int r;
-  if (lds_for(8) <= 80 * 1024) {
+  if (d.raw_src) {   // the stem on the raw images (conv_small_raw_applies: 8 rows fit two workgroups per CU)
+    const size_t l = lds_for(8);
+    r = nco == 1 ? launch_small_nj<3, 8, bf16_t, 1, false, 2, 4, true>(a, s, WS, PS, l)
+      : nco == 2 ? launch_small_nj<3, 8, bf16_t, 2, false, 2, 4, true>(a, s, WS, PS, l)
+                 : launch_small_nj<3, 8, bf16_t, 4, false, 2, 4, true>(a, s, WS, PS, l);
+  } else if (lds_for(8) <= 80 * 1024) {
     const size_t l = lds_for(8);
     r = nco == 1 ? launch_small_nj<3, 8, bf16_t, 1, false, 2>(a, s, WS, PS, l)
       : nco == 2 ? launch_small_nj<3, 8, bf16_t, 2, false, 2>(a, s, WS, PS, l)
@@ -353,10 +407,25 @@ static int pick_th(const ConvArgs& a, hipStream_t s, int WS, int PS, int force_t
   return r < 0 ? r : 1;
 }
 
+// Whether the raw-image staging form (hiseg_conv2d_desc.raw_src) takes the layer: the stride-2 3x3 form of
+// conv_small_try with one 8-channel source (the three image channels, zero-padded) and no SE gate, its weights and an
+// 8-row halo within two workgroups per CU, the image planes and tables addressable as f32.
+bool conv_small_raw_applies(const ConvArgs& a) {
+  const hiseg_conv2d_desc& d = a.d;
+  if (!d.raw_src || !d.raw_mean || !d.raw_std || !d.raw_max) return false;
+  if (((uintptr_t)d.raw_src | (uintptr_t)d.raw_mean | (uintptr_t)d.raw_std | (uintptr_t)d.raw_max) & 3) return false;
+  if (d.dtype != HISEG_BF16 || d.out_dtype != HISEG_BF16 || d.convT || d.stride != 2 || d.a_up != 1) return false;
+  if (d.KH != 3 || d.KW != 3 || d.pad != 1 || d.Ho != (d.H - 1) / 2 + 1 || d.Wo != (d.W - 1) / 2 + 1) return false;
+  if (d.Ca != 8 || d.Cb != 0 || d.in_scale || d.K_pad < 72 || d.K_pad % 64) return false;
+  const size_t lds = (size_t)d.Cout_pad * odd_slots(d.K_pad / 8) * 16 + (size_t)(7 * 2 + 3) * (63 * 2 + 3) * 16;
+  return lds <= 80 * 1024;
+}
+
 // Returns 1 if launched, 0 if the layer does not qualify, <0 on error.
 // variant: 0 auto, 50 auto TH, 51/52/54/58 force TH = 1/2/4/8.
 int conv_small_try(const ConvArgs& a, hipStream_t s, int variant) {
   const hiseg_conv2d_desc& d = a.d;
+  if (d.raw_src && !conv_small_raw_applies(a)) return 0;
   if (d.dtype != HISEG_BF16 || d.convT || (d.stride != 1 && d.stride != 2)) return 0;
   if (!(d.KH == d.KW && (d.KH == 1 || d.KH == 3) && d.pad == d.KH / 2)) return 0;
   const bool s2 = d.stride == 2;

@@ -840,14 +840,7 @@ static int dw_quads_per_block(int nq) {
 }
 
 // ------------------------------------------------------------------ input prologue
-__device__ __forceinline__ unsigned ord_enc(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord_dec(unsigned e) {
-  return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e);
-}
-
+// (ord_enc / ord_dec, the order-preserving encoding of the maximum: common.h)
 __global__ void reset_max_kernel(unsigned* buf) { *buf = 0u; }  // encodes below -FLT_MAX
 
 __global__ void __launch_bounds__(256) image_max_kernel(const float* x, long long n, unsigned* buf) {

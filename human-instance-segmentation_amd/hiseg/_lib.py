@@ -146,6 +146,7 @@ class Conv2dDesc(Desc):
         ("px_scale", c_void_p),
         ("head2_w", c_void_p), ("head2_b", c_void_p), ("head2_out", c_void_p),
         ("a_gate", c_void_p), ("res_gate", c_void_p),
+        ("raw_src", c_void_p), ("raw_mean", c_void_p), ("raw_std", c_void_p), ("raw_max", c_void_p),
     ]
 
 
@@ -559,7 +560,8 @@ def bn_last_path():
     return bn_path_decode(lib().hiseg_bn_last_path())
 
 
-CONV_PATHS = ("generic", "generic_splitk", "fast", "wide", "hw", "hwr", "hwt", "hwc", "pw", "small", "rows", "resblock")
+CONV_PATHS = ("generic", "generic_splitk", "fast", "wide", "hw", "hwr", "hwt", "hwc", "pw", "small", "rows", "resblock",
+              "stem_raw")
 
 
 def conv_last_path():

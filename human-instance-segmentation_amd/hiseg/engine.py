@@ -163,6 +163,9 @@ def _check_input(x: torch.Tensor, what: str):
 # residual_block takes the one-launch form of a 64-channel block (ops.resblock) where the library has it; False runs
 # every block as two launches (the tests' bit-for-bit comparison; not a setting of the product)
 RESBLOCK_FUSED = True
+# unet_logit_iter hands the raw images to the EfficientNet stem where the library normalises inside that layer
+# (ops.stem_raw); False runs input_norm + stem (the tests' bit-for-bit comparison; not a setting of the product)
+STEM_RAW = True
 
 
 def _block_acts(blk: nn.Module) -> Tuple[int, int]:
@@ -530,8 +533,23 @@ def unet_logit_iter(E: Ctx, pre: nn.Module, images: torch.Tensor):
     B, _, H, W = images.shape
     if H % 32 or W % 32:
         raise NotImplementedError(f"image size {H}x{W} must be a multiple of 32 for the EfficientNet-UNet")
-    x = ops.input_norm(images, E.f32(pre.norm_mean, (3,)), E.f32(pre.norm_std, (3,)), E.dtype)
-    return (yield from effunet_forward_iter(E, pre.model, x))
+    return (yield from effunet_forward_iter(E, pre.model, unet_input(E, pre, images)))
+
+
+def unet_input(E: Ctx, pre: nn.Module, images: torch.Tensor):
+    """normalize_input for the smp.Unet.  The stem conv is the normalised images' only reader: where the library
+    has that form it normalises as it stages them, and this returns ops.RawImages (the maximum launched, no
+    normalised copy written) for effunet_stem; the normalised NHWC Act otherwise."""
+    enc = pre.model.encoder
+    stem = E.conv(enc.conv_stem, enc.bn1, ACT_SILU) if STEM_RAW else None
+    return ops.input_norm(images, E.f32(pre.norm_mean, (3,)), E.f32(pre.norm_std, (3,)), E.dtype, stem=stem)
+
+
+def effunet_stem(E: Ctx, enc: nn.Module, x) -> Act:
+    """conv_stem + bn1 + SiLU on unet_input's result (an Act, or ops.RawImages: one launch normalises and convolves)."""
+    if isinstance(x, ops.RawImages):
+        return ops.stem_raw(x)
+    return ops.conv2d(E.conv(enc.conv_stem, enc.bn1, ACT_SILU), x)
 
 
 def effunet_forward(E: Ctx, net: nn.Module, x: Act) -> torch.Tensor:
@@ -539,11 +557,12 @@ def effunet_forward(E: Ctx, net: nn.Module, x: Act) -> torch.Tensor:
     return _drain(effunet_forward_iter(E, net, x))
 
 
-def effunet_forward_iter(E: Ctx, net: nn.Module, x: Act):
-    """effunet_forward as a generator: yields after the stem, each MBConv block and each decoder block."""
+def effunet_forward_iter(E: Ctx, net: nn.Module, x):
+    """effunet_forward as a generator: yields after the stem, each MBConv block and each decoder block.  ``x``: the
+    normalised NHWC input, or ops.RawImages (unet_input: the stem normalises)."""
     B, H, W = x.N, x.H, x.W
     enc = net.encoder
-    x = ops.conv2d(E.conv(enc.conv_stem, enc.bn1, ACT_SILU), x)
+    x = effunet_stem(E, enc, x)
     feats = [x]
     yield
     for si, stage in enumerate(enc.blocks):

@@ -585,17 +585,102 @@ def dwconv_se_gate(x: Act, w: torch.Tensor, scale: torch.Tensor, shift: torch.Te
     return out, gate
 
 
-def input_norm(images: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, dtype: torch.dtype) -> Act:
-    """normalize_input (hierarchical_segmentation_unet.py:1885-1890) with a device-side max flag."""
+def image_max(x: torch.Tensor) -> torch.Tensor:
+    """The device-side maximum of a contiguous f32 batch (hiseg_image_max_fwd's encoded buffer): the /255 flag of
+    normalize_input, read by the kernel that normalises."""
+    maxbuf = torch.empty(1, dtype=torch.float32, device=x.device)
+    L.check(L.lib().hiseg_image_max_fwd(x.data_ptr(), x.numel(), maxbuf.data_ptr(), L.stream_ptr()), "image_max")
+    return maxbuf
+
+
+@dataclass
+class RawImages:
+    """The f32 NCHW image batch standing in for its normalised NHWC activation: the stem conv normalises it while it
+    stages its halo (stem_raw), so that activation is never stored.  ``plan``: that conv; ``maxbuf``: image_max of
+    the batch."""
+    plan: ConvPlan
+    t: torch.Tensor
+    mean: torch.Tensor
+    std: torch.Tensor
+    maxbuf: torch.Tensor
+    dtype: torch.dtype
+
+    @property
+    def N(self) -> int:
+        return self.t.shape[0]
+
+    @property
+    def H(self) -> int:
+        return self.t.shape[2]
+
+    @property
+    def W(self) -> int:
+        return self.t.shape[3]
+
+
+def input_norm(images: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, dtype: torch.dtype,
+               stem: Optional[ConvPlan] = None):
+    """normalize_input (hierarchical_segmentation_unet.py:1885-1890) with a device-side max flag.  ``stem``: the
+    plan of the one conv that reads the result; where the library normalises inside that layer
+    (stem_raw_ok) the images come back as :class:`RawImages` for stem_raw and no normalised copy is written; an
+    :class:`Act` otherwise.  The maximum is a reduction over the whole batch and is launched first either way."""
     _require_gpu(images)
+    raw_ok = stem is not None and stem_raw_ok(stem, images, dtype)
     x = images.contiguous().float()
     B, C, H, W = x.shape
-    lib = L.lib()
-    maxbuf = torch.empty(1, dtype=torch.float32, device=x.device)
-    L.check(lib.hiseg_image_max_fwd(x.data_ptr(), x.numel(), maxbuf.data_ptr(), L.stream_ptr()), "image_max")
+    maxbuf = image_max(x)
+    if raw_ok:
+        return RawImages(stem, x, mean, std, maxbuf, dtype)
     out = Act.new(B, H, W, C, dtype, x.device, zero=False)
-    L.check(lib.hiseg_input_norm_fwd(hdtype(dtype), x.data_ptr(), B, C, H, W, maxbuf.data_ptr(), mean.data_ptr(),
-                                     std.data_ptr(), out.ptr(), out.cstride, L.stream_ptr()), "input_norm")
+    L.check(L.lib().hiseg_input_norm_fwd(hdtype(dtype), x.data_ptr(), B, C, H, W, maxbuf.data_ptr(), mean.data_ptr(),
+                                         std.data_ptr(), out.ptr(), out.cstride, L.stream_ptr()), "input_norm")
+    return out
+
+
+def _stem_raw_desc(p: ConvPlan, images: torch.Tensor, mean, std, maxbuf, out: Optional[Act]):
+    """The Conv2dDesc of the stem conv reading raw images (hiseg_conv2d_desc.raw_src).  Source A is described as the
+    8-channel NHWC view the images stand for and is not read."""
+    B, _, H, W = images.shape
+    d = L.Conv2dDesc()
+    d.dtype = d.out_dtype = L.HISEG_BF16
+    d.N, d.H, d.W = B, H, W
+    d.Ho = (H + 2 * p.pad - p.kh) // p.stride + 1
+    d.Wo = (W + 2 * p.pad - p.kw) // p.stride + 1
+    d.KH, d.KW, d.stride, d.pad = p.kh, p.kw, p.stride, p.pad
+    d.a_cstride, d.a_coff, d.Ca, d.a_up = p.ca, 0, p.ca, 1
+    d.weight, d.Cout, d.Cout_pad, d.K_pad = p.weight, p.gemm_cols, p.cout_pad, p.k_pad
+    d.scale, d.shift, d.act, d.act_beta = p.scale, p.shift, int(p.act), L.act_beta(p.act)
+    if out is not None:
+        d.out, d.o_cstride, d.o_coff = out, out.cstride, out.coff
+    else:
+        d.out, d.o_cstride, d.o_coff = p.weight, round_up(p.cout, 8), 0   # (a plan: any aligned address)
+    d.raw_src, d.raw_mean, d.raw_std, d.raw_max = images, mean, std, maxbuf
+    return d
+
+
+def stem_raw_ok(p: ConvPlan, images: torch.Tensor, dtype: torch.dtype) -> bool:
+    """Whether the library runs this stem conv straight from ``images`` (planning only, no launch): bf16 compute,
+    contiguous f32 [B, 3, H, W] on the GPU, a single-source 3x3 stride-2 layer, every operand under 2 GiB
+    (hiseg_conv2d_fused_ok).  A launch hook that wants every layer as a plain conv (RECORD) gets the two passes."""
+    if RECORD is not None or dtype != torch.bfloat16 or images.dim() != 4 or images.shape[1] != 3 or \
+            images.dtype != torch.float32 or not images.is_cuda or not images.is_contiguous():
+        return False
+    if p.convT or (p.kh, p.kw, p.stride, p.pad) != (3, 3, 2, 1) or p.cb or p.weight.dtype != torch.bfloat16:
+        return False
+    # (the tables' addresses: the plan looks at their alignment only)
+    d = _stem_raw_desc(p, images, p.scale, p.scale, p.scale, None)
+    return bool(L.lib().hiseg_conv2d_fused_ok(ctypes.byref(d)))
+
+
+def stem_raw(raw: RawImages) -> Act:
+    """The stem conv on raw images (input_norm asked stem_raw_ok): the bits of conv2d(plan, input_norm(images)),
+    recorded as path ("stem_raw", 1)."""
+    p, x = raw.plan, raw.t
+    out = Act.new(raw.N, (raw.H - 1) // 2 + 1, (raw.W - 1) // 2 + 1, p.cout, raw.dtype, x.device)
+    d = _stem_raw_desc(p, x, raw.mean, raw.std, raw.maxbuf, out)
+    if GATE is not None:   # (far below GATE.min_flops: a light launch, as the plain stem conv is)
+        GATE.light()
+    L.check(L.lib().hiseg_conv2d_fwd(ctypes.byref(d), L.stream_ptr()), "stem_raw")
     return out
 
 

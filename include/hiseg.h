@@ -183,12 +183,21 @@ typedef struct hiseg_conv2d_desc {
    *                           together with head2_out (the 128-Cout residual form above).
    * Both tables 16-B aligned.  Ask hiseg_conv2d_fused_ok first, the call fails where that returns 0. */
   const float* a_gate; const float* res_gate;
+  /* Optional (round 10, the EfficientNet stem): source A is the raw f32 NCHW image batch [N][3][H][W] (contiguous,
+   * 4-B aligned) and the layer normalises it while it stages its halo, in place of a hiseg_input_norm_fwd pass:
+   * v / 255 when the device-side maximum raw_max (hiseg_image_max_fwd's buffer) decodes to > 1, then
+   * (v - raw_mean[c]) / raw_std[c], each operation rounded on its own, rounded to bf16 and zero-padded to the
+   * layer's 8 input channels -- the bits hiseg_input_norm_fwd stores.  srcA / a_cstride / a_coff are then not read
+   * (srcA may be NULL).  Only the halo-tiled direct kernel's 3x3 stride-2 form with Ca == 8, one source, no
+   * in_scale, a bf16 output and no other fused operand has it: ask hiseg_conv2d_fused_ok first, the call fails
+   * where that returns 0.  The launch is recorded as path HISEG_CONV_PATH_STEM_RAW * 10000 + 1. */
+  const float* raw_src; const float* raw_mean; const float* raw_std; const float* raw_max;
 } hiseg_conv2d_desc;
 int hiseg_conv2d_fwd(const hiseg_conv2d_desc* d, hiseg_stream_t stream);
 /* 1 when hiseg_conv2d_fwd's automatic choice has a kernel that honours d->px_scale / d->head2_out / d->a_gate /
- * d->res_gate (every one of them that is set) for this layer (no launch); 0: the caller runs the separate passes
- * (hiseg_pixel_scale_fwd / hiseg_channel_scale_fwd before the conv; the conv, then hiseg_hier_combine_fwd on its
- * output). */
+ * d->res_gate / d->raw_src (every one of them that is set) for this layer (no launch); 0: the caller runs the
+ * separate passes (hiseg_pixel_scale_fwd / hiseg_channel_scale_fwd / hiseg_input_norm_fwd before the conv; the conv,
+ * then hiseg_hier_combine_fwd on its output). */
 int hiseg_conv2d_fused_ok(const hiseg_conv2d_desc* d);
 /* A whole 64-channel ResidualBlock, y = act2(bn2(conv2(act1(bn1(conv1(x))))) + x), in one launch: d1 describes conv1
  * (srcA = x, no residual; its `out` is not written), d2 conv2 (residual = x with conv1's source stride and offset,
@@ -235,7 +244,8 @@ int hiseg_conv2d_fwd_variant(const hiseg_conv2d_desc* d, int variant, hiseg_stre
 #define HISEG_CONV_PATH_SMALL 9
 #define HISEG_CONV_PATH_ROWS 10
 #define HISEG_CONV_PATH_RESBLOCK 11
-#define HISEG_CONV_PATH_FAMILIES 12
+#define HISEG_CONV_PATH_STEM_RAW 12
+#define HISEG_CONV_PATH_FAMILIES 13
 int hiseg_conv2d_last_path(void);
 int hiseg_conv2d_path_stats(long long* counts, int n, int reset);
 

@@ -168,9 +168,67 @@ def resblock_bench(args):
     print("resblock64_64x48", json.dumps(row), flush=True)
 
 
+def stem_bench(args):
+    """--stem: the EfficientNet-B0 stem (3 -> 32, 3x3 stride 2, SiLU) at the bench batch, 32 x 3 x 480 x 640, reading the
+    raw images (hiseg_conv2d_desc.raw_src) against the two launches it replaces -- hiseg_input_norm_fwd, then the stem
+    on the normalised NHWC copy -- interleaved in one process, best round; bit-equality of the outputs; ms and
+    algorithmic GB/s (two launches: images in, copy out, copy in, output out; raw: images in, output out).  The
+    maximum (hiseg_image_max_fwd) runs once, outside the timing: both forms need it."""
+    B, H, W, C = 32, 480, 640, 32
+    dt = torch.bfloat16
+    g = torch.Generator(device=DEV).manual_seed(0)
+    images = torch.rand(B, 3, H, W, device=DEV, generator=g) * 255
+    w = torch.randn(C, 3, 3, 3, device=DEV, generator=g) / 27 ** 0.5
+    p = ops.pack_conv(w, torch.randn(C, device=DEV, generator=g) * 0.1, None, L.ACT_SILU, dt, DEV, stride=2, pad=1)
+    mean = torch.tensor([0.485, 0.456, 0.406], device=DEV)
+    std = torch.tensor([0.229, 0.224, 0.225], device=DEV)
+    assert ops.stem_raw_ok(p, images, dt), "the stem must have the raw form"
+    maxbuf = ops.image_max(images)
+    xn = ops.Act.new(B, H, W, 3, dt, DEV, zero=False)
+    y2, y1 = (ops.Act.new(B, H // 2, W // 2, C, dt, DEV, zero=False) for _ in range(2))
+    d2 = ops._conv_desc(p, xn, None, None, None, y2)
+    d1 = ops._stem_raw_desc(p, images, mean, std, maxbuf, y1)
+
+    def pair():
+        L.check(L.lib().hiseg_input_norm_fwd(ops.hdtype(dt), images.data_ptr(), B, 3, H, W, maxbuf.data_ptr(),
+                                             mean.data_ptr(), std.data_ptr(), xn.ptr(), xn.cstride, L.stream_ptr()),
+                "input_norm")
+        L.check(L.lib().hiseg_conv2d_fwd(ctypes.byref(d2), L.stream_ptr()), "stem")
+
+    def raw():
+        L.check(L.lib().hiseg_conv2d_fwd(ctypes.byref(d1), L.stream_ptr()), "stem_raw")
+
+    y1.t.fill_(float("nan"))
+    y2.t.fill_(float("nan"))
+    pair()
+    raw()
+    torch.cuda.synchronize()
+    same = bool(torch.equal(y1.t, y2.t))
+    times = {"pair": [], "raw": []}
+    for _ in range(args.rounds):
+        for name, fn in (("pair", pair), ("raw", raw)):
+            for _ in range(3):
+                fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) / args.reps)
+    img, copy, out = 4.0 * images.numel(), 2.0 * xn.t.numel(), 2.0 * y1.t.numel()
+    row = {"bit_equal": same}
+    for name, nbytes in (("pair", img + 2 * copy + out), ("raw", img + out)):
+        ms = min(times[name])
+        row[name] = {"ms": round(ms, 4), "alg_gbs": round(nbytes / ms / 1e6, 1),
+                     "rounds_ms": [round(v, 4) for v in times[name]]}
+    print("stem_3to32_3x3s2_480x640", json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--resblock", action="store_true", help="time the fused 64-channel ResidualBlock against its pair")
+    ap.add_argument("--stem", action="store_true", help="time the stem on raw images against input_norm + stem")
     ap.add_argument("--variants", default="-1,0,1,2,4")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
@@ -179,6 +237,8 @@ def main():
     args = ap.parse_args()
     if args.resblock:
         return resblock_bench(args)
+    if args.stem:
+        return stem_bench(args)
     variants = [int(v) for v in args.variants.split(",")]
     results = {}
     for name in args.shapes.split(","):
