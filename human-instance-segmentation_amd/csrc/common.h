@@ -141,6 +141,10 @@ template <> struct Chunk<bf16_t> {
   }
 };
 
+// Host-side launch arithmetic of the 16-B-chunk kernels: elements per chunk, blocks of bs threads over n items.
+inline int chunk_of(int dtype) { return dtype == HISEG_BF16 ? 8 : 4; }
+inline unsigned nblocks(long long n, int bs) { return (unsigned)((n + bs - 1) / bs); }
+
 }  // namespace hiseg
 
 // Host-side error plumbing (defined in capi.cpp).

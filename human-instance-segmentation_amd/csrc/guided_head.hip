@@ -255,8 +255,6 @@ __global__ void __launch_bounds__(kT) guided_finish_kernel(hiseg_guided_finish_d
   }
 }
 
-int chunk_of(int dtype) { return dtype == HISEG_BF16 ? 8 : 4; }
-
 // rows of output per workgroup and the LDS rows that covers (with slack for the device's fused multiply-add)
 bool finish_plan(int h, int w, int mh, int mw, int* rows, int* cap_rows) {
   const bool same = mh == h && mw == w;

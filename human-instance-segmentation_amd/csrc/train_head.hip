@@ -946,8 +946,6 @@ using namespace hiseg;
     }                                 \
   } while (0)
 
-static int chunk_of(int dtype) { return dtype == HISEG_BF16 ? 8 : 4; }
-
 // train_norm.hip: the BatchNorm statistics merge over an explicit split count
 int bn_finalize_splits(const float* partial, int S, int C, long long P, const float* gamma, const float* beta,
                        float eps, float momentum, float* running_mean, float* running_var, float* mean, float* invstd,

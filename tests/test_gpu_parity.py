@@ -1450,6 +1450,50 @@ on the stride-2 and narrow layers the automatic choice gives the gather kernel."
     assert torch.equal(g_one[0], g1[0])
 
 
+@pytest.mark.parametrize("knob", [None, ("HISEG_DWCONV_T", "0"), ("HISEG_DWCONV_T", "2"), ("HISEG_DWCONV_Q", "0")],
+                         ids=["default", "T0", "T2", "Q0"])
+@pytest.mark.parametrize("C,dt", [(32, torch.bfloat16), (64, torch.bfloat16), (200, torch.bfloat16), (8, torch.float32)])
+@pytest.mark.parametrize("k,stride", [(3, 1), (3, 2), (5, 1), (5, 2)])
+def test_dwconv_gap_parts_is_what_the_kernel_writes(k, stride, C, dt, knob, monkeypatch):
+    """hiseg_dw_gap_parts (what callers size the SE partial buffer by) is exactly the number of partial rows per image
+    hiseg_dwconv_gap_fwd writes, for every kernel the depthwise plan can choose: a NaN-filled buffer of 64 rows x N x C
+    floats holds finite values in its first N * parts * C floats and NaN in every float after them.  9 x 17 is ragged
+    against the 8 x 16 tile and the 4-pixel strip; C = 32 the quad gather, 64 the tile's lower bound, 200 a ragged
+    channel group, 8 in f32 the f32 gather; the knobs are read per call.  The expected regime is asserted too (tile
+    count where the LDS-tiled kernel runs, hiseg_dw_gap_tiles elsewhere), so the cases cannot all sit on one kernel."""
+    from hiseg import _lib as L
+    from hiseg import ops
+    N, H, W, ROWS = 2, 9, 17, 64
+    if knob:
+        monkeypatch.setenv(*knob)
+    g = torch.Generator(device=DEV).manual_seed(47)
+    A = ops.Act.from_nchw(torch.randn(N, C, H, W, device=DEV, generator=g), dt)
+    wd = (torch.randn(k * k, C, device=DEV, generator=g) * 0.3).contiguous()
+    sc, sh = torch.rand(C, device=DEV, generator=g) + 0.5, torch.randn(C, device=DEV, generator=g) * 0.1
+    Ho, Wo = (H + 2 * (k // 2) - k) // stride + 1, (W + 2 * (k // 2) - k) // stride + 1
+    lib = L.lib()
+    parts = lib.hiseg_dw_gap_parts(ops.hdtype(dt), N, Ho, Wo, C, k, stride)
+    bf16 = dt == torch.bfloat16
+    t_mode = knob[1] if knob and knob[0] == "HISEG_DWCONV_T" else "1"
+    q_on = not (knob and knob[0] == "HISEG_DWCONV_Q")
+    tiled = bf16 and q_on and (t_mode == "2" or (t_mode == "1" and C < 2048 and
+                                                 ((stride == 1 and C >= 64) or (k == 5 and C >= 192))))
+    if tiled:
+        assert parts == -(-Ho // 8) * -(-Wo // 16)
+    else:
+        assert parts == lib.hiseg_dw_gap_tiles(N, Ho, Wo)
+    assert 0 < parts < ROWS
+    out = ops.Act.new(N, Ho, Wo, C, dt, A.t.device, zero=False)
+    partial = torch.full((ROWS * N * C,), float("nan"), dtype=torch.float32, device=DEV)
+    L.check(lib.hiseg_dwconv_gap_fwd(ops.hdtype(dt), A.ptr(), N, H, W, C, k, stride, wd.data_ptr(), sc.data_ptr(),
+                                     sh.data_ptr(), 3, out.ptr(), Ho, Wo, partial.data_ptr(), L.stream_ptr()),
+            "dwconv_gap")
+    torch.cuda.synchronize()
+    used = N * parts * C
+    assert torch.isfinite(partial[:used]).all()
+    assert torch.isnan(partial[used:]).all()
+
+
 @pytest.mark.parametrize("case", [(4, 20, 20, 3840, 160, 5, 1), (2, 40, 40, 240, 10, 3, 2), (3, 15, 11, 104, 25, 3, 1),
                                   (2, 9, 7, 1152, 48, 5, 1), (1, 30, 30, 2304, 96, 3, 1)])
 def test_se_two_launch_matches_three_launch_and_f64(case, monkeypatch):
