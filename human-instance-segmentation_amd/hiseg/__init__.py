@@ -2,16 +2,18 @@
 
 Drop-in for the RGB hierarchical path of PINTO0309/human-instance-segmentation
 (HierarchicalRGBSegmentationModelWithFullImagePretrainedUNet + RefinedHierarchicalSegmentationHead
-on a full-image EfficientNet-UNet).  Module tree and state_dict keys follow the reference;
+on a full-image EfficientNet-UNet, and the plain HierarchicalRGBSegmentationModel).  Module tree and state_dict keys follow the reference;
 every forward runs on libhiseg (hand-written gfx950 HIP kernels, C ABI in include/hiseg.h).
 """
 from .layers import (  # noqa: F401
     BoundaryRefinementModule, ChannelAttentionModule, ContourDetectionBranch, DistanceTransformDecoder, EnhancedUNet,
-    ExtendedHierarchicalSegmentationHeadUNetV2, LayerNorm2d, PretrainedUNetGuidedSegmentationHead,
-    RefinedHierarchicalSegmentationHead, ResidualBlock, SpatialAttentionModule)
+    ExtendedHierarchicalSegmentationHeadUNetV2, HierarchicalSegmentationHeadUNetV2, LayerNorm2d,
+    PretrainedUNetGuidedSegmentationHead, RefinedHierarchicalSegmentationHead, ResidualBlock, RGBFeatureExtractor,
+    SpatialAttentionModule)
 from .effunet import EfficientNetUnet  # noqa: F401
 from .model import (  # noqa: F401
-    DynamicRoIAlign, HierarchicalRGBSegmentationModelWithFullImagePretrainedUNet, PreTrainedPeopleSegmentationUNet,
+    DynamicRoIAlign, HierarchicalRGBSegmentationModel, HierarchicalRGBSegmentationModelWithFullImagePretrainedUNet,
+    PreTrainedPeopleSegmentationUNet,
     PreTrainedPeopleSegmentationUNetWrapper, RGBHierarchicalExportWrapper, StreamPipelinedExport,
     create_rgb_hierarchical_model)
 

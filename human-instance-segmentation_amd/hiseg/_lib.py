@@ -328,6 +328,8 @@ def _declare(lib):
         "hiseg_input_norm_fwd": ([c_int, P, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P], c_int),
         "hiseg_hier_combine_fwd": ([c_int, P, c_int, c_int, c_int, P, c_int, P, P, P, c_int, c_float, c_int, P, P,
                                     P, P, P, P, P, P], c_int),
+        "hiseg_hier_combine_resize": ([P, c_int, c_int, c_int, P, P, P, P, c_int, c_float, c_int, P, P, c_int, c_int,
+                                       P, P, P, P], c_int),
         "hiseg_ubf_ln_tables": ([P, c_int, c_int, c_int, P, P, P, P, c_float, c_int, P, P, P, P, P], c_int),
         "hiseg_nhwc_to_nchw_fwd": ([c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P], c_int),
         "hiseg_nchw_to_nhwc_fwd": ([c_int, P, c_int, c_int, c_int, c_int, P, c_int, P], c_int),

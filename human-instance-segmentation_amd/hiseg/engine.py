@@ -222,6 +222,20 @@ def rgb_feature_extractor(E: Ctx, seq: nn.Sequential, x: Act, out: Optional[Act]
     return cna(E, seq[12], seq[13], act_code(seq[14]), h, out=out)
 
 
+def rgb_extractor_plain(E: Ctx, seq: nn.Sequential, x: Act) -> Act:
+    """RGBFeatureExtractor.features (hierarchical_segmentation_rgb.py:253-281): conv + norm + act per layer, a
+    residual block after every layer but the first."""
+    mods = list(seq)
+    i = 0
+    while i < len(mods):
+        x = cna(E, mods[i], mods[i + 1], act_code(mods[i + 2]), x)
+        i += 3
+        if i < len(mods) and not isinstance(mods[i], nn.Conv2d):
+            x = residual_block(E, mods[i], x)
+            i += 1
+    return x
+
+
 def enhanced_unet(E: Ctx, u: nn.Module, x: Act) -> Tuple[Act, Act]:
     """EnhancedUNet.forward (hierarchical_segmentation_unet.py:375-417).
 
@@ -270,8 +284,11 @@ def enhanced_unet(E: Ctx, u: nn.Module, x: Act) -> Tuple[Act, Act]:
 
 def hier_head(E: Ctx, head: nn.Module, feat: Act, aux: str) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
     """RefinedHierarchicalSegmentationHead.forward (refinement.py:734-804) over
-    ExtendedHierarchicalSegmentationHeadUNetV2.forward (:550-606)."""
-    bh = head.base_head
+    ExtendedHierarchicalSegmentationHeadUNetV2.forward (:550-606).  A HierarchicalSegmentationHeadUNetV2 (unet.py
+    :775-845, the plain RGB model's head without a refinement flag) is the same walk with no refiner and no aux
+    branch, and its aux dict has no ``shared_features``."""
+    bh = getattr(head, "base_head", head)
+    plain = bh is head
     sf = bh.shared_features
     s = cna(E, sf[0], sf[1], act_code(sf[2]), feat)
     s = residual_block(E, sf[4], s)
@@ -310,8 +327,7 @@ def hier_head(E: Ctx, head: nn.Module, feat: Act, aux: str) -> Tuple[torch.Tenso
     tH, tW = t.H, t.W
     t = residual_block(E, blk, t, head2=h2, in_gate=gate)
     mh, mw = bh.mask_height, bh.mask_width
-    if (tH, tW) != (mh, mw) or (2 * low.H, 2 * low.W) != (mh, mw):
-        raise NotImplementedError(f"mask size {mh}x{mw} must be 2x the ROI size {low.H}x{low.W} on the hiseg path")
+    assert (tH, tW) == (2 * low.H, 2 * low.W)
     up = bh.upsample_bg_fg
     per_sample = isinstance(up[1], LayerNorm2d)
     if per_sample:   # LayerNorm2d over the ConvTranspose output: per-ROI tables [N][32]
@@ -324,11 +340,21 @@ def hier_head(E: Ctx, head: nn.Module, feat: Act, aux: str) -> Tuple[torch.Tenso
     else:
         ut_s, ut_h = E.affine(("ut", id(up[0])), up[0].out_channels, up[0].bias, up[1])
     want = aux == "full"
-    logits, bgfg, tn = ops.hier_combine(
-        low.t, low.N, low.H, low.W, t, E.f32(up[0].weight), ut_s, ut_h, act_code(up[2]),
-        E.f32(up[3].weight, (2, up[3].in_channels)), E.f32(up[3].bias),
-        h2.w, h2.b, want, per_sample=per_sample, tn2=h2.out)
-    if head.use_boundary_refinement:   # refines the returned masks only; the aux tensors stay (refinement.py:767-769)
+    if (mh, mw) == (tH, tW):
+        logits, bgfg, tn = ops.hier_combine(
+            low.t, low.N, low.H, low.W, t, E.f32(up[0].weight), ut_s, ut_h, act_code(up[2]),
+            E.f32(up[3].weight, (2, up[3].in_channels)), E.f32(up[3].bias),
+            h2.w, h2.b, want, per_sample=per_sample, tn2=h2.out)
+    else:   # the reference resizes both branches from 2 x ROI to the mask size, then combines (refinement.py:559-596)
+        tn2 = h2.out
+        if t is not None:   # the branch's last conv had no Head2 epilogue: its 1x1 first, two f32 logits per pixel
+            tq = Act.new(t.N, tH, tW, 2, torch.float32, E.device, cpad=2, zero=False)
+            ops.conv2d(E.conv(last), t, out=tq)
+            tn2 = tq.t
+        logits, bgfg, tn = ops.hier_combine_resize(
+            low.t, low.N, low.H, low.W, tn2, E.f32(up[0].weight), ut_s, ut_h, act_code(up[2]),
+            E.f32(up[3].weight, (2, up[3].in_channels)), E.f32(up[3].bias), mh, mw, want, per_sample=per_sample)
+    if not plain and head.use_boundary_refinement:   # refines the returned masks only; the aux tensors stay (refinement.py:767-769)
         logits = boundary_refine(E, head.boundary_refiner, logits)
     auxd: Dict[str, torch.Tensor] = {}
     if not want:
@@ -336,8 +362,11 @@ def hier_head(E: Ctx, head: nn.Module, feat: Act, aux: str) -> Tuple[torch.Tenso
     fg_att = ops.conv2d(E.conv(fg[5], None, ACT_SIGMOID), g)
     auxd.update({
         "bg_fg_logits": bgfg, "bg_fg_logits_low": low.to_nchw(), "target_nontarget_logits": tn,
-        "fg_attention": fg_att.to_nchw(), "shared_features": s.to_nchw(),
+        "fg_attention": fg_att.to_nchw(),
     })
+    if plain:
+        return logits, auxd
+    auxd["shared_features"] = s.to_nchw()
     lib = L.lib()
     if head.use_contour_detection:
         cb = head.contour_branch.contour_branch
@@ -689,6 +718,32 @@ def rgb_model_forward(model: nn.Module, images: torch.Tensor, rois: torch.Tensor
     return logits, auxd
 
 
+def rgb_plain_forward(model: nn.Module, images: torch.Tensor, rois: torch.Tensor, aux: str = "full"):
+    """HierarchicalRGBSegmentationModel.forward (hierarchical_segmentation_rgb.py:410-439): RoIAlign (aligned=False)
+    of the images, RGBFeatureExtractor, hierarchical head.  ``aux`` "full" adds ``roi_patches``, the RoIAligned RGB
+    as f32 NCHW."""
+    _check_input(images, "HierarchicalRGBSegmentationModel")
+    if model.training:
+        raise NotImplementedError("hiseg executes the inference (eval-mode) forward; call model.eval()")
+    dev = images.device
+    E = Ctx(model, _root_dtype(model), dev)
+    images = images.contiguous().float()
+    rois = rois.to(device=dev, dtype=torch.float32).contiguous()
+    N = rois.shape[0]
+    rh, rw = model.roi_height, model.roi_width
+    ra = model.roi_align
+    rgb = Act.new(N, rh, rw, 3, E.dtype, dev, zero=False)
+    ops.roi_align(images, rois, rh, rw, ra.spatial_scale_h, ra.spatial_scale_w, ra.aligned, out=rgb,
+                  zero_to=rgb.cstride)
+    feats = rgb_extractor_plain(E, model.rgb_extractor.features, rgb)
+    logits, auxd = hier_head(E, model.segmentation_head, feats, aux)
+    if aux == "full":
+        rp = torch.empty(N, 3, rh, rw, dtype=torch.float32, device=dev)
+        ops.roi_align(images, rois, rh, rw, ra.spatial_scale_h, ra.spatial_scale_w, ra.aligned, nchw_out=rp)
+        auxd["roi_patches"] = rp
+    return logits, auxd
+
+
 def export_forward(model: nn.Module, images: torch.Tensor, rois: torch.Tensor, dilation: int = 0):
     """Exported contract: (instance_masks [N,1,mh,mw], binary_masks [B,1,H,W])."""
     logits, auxd = rgb_model_forward(model, images, rois, aux="none")
@@ -767,6 +822,6 @@ def guided_head_nchw(head: nn.Module, features: torch.Tensor, bg_fg_mask: torch.
 
 
 def head_nchw(head: nn.Module, x: torch.Tensor):
-    _check_input(x, "RefinedHierarchicalSegmentationHead")
+    _check_input(x, type(head).__name__)
     E = Ctx(head, _root_dtype(head), x.device)
     return hier_head(E, head, Act.from_nchw(x, E.dtype), "full")

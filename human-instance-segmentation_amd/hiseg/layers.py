@@ -281,6 +281,63 @@ class ExtendedHierarchicalSegmentationHeadUNetV2(nn.Module):
             nn.Conv2d(m // 4, half, 1), make_act(act, beta), nn.Conv2d(half, m, 1), nn.Sigmoid())
 
 
+class HierarchicalSegmentationHeadUNetV2(ExtendedHierarchicalSegmentationHeadUNetV2):
+    """The head of the plain RGB model when no refinement flag is set --
+    advanced/hierarchical_segmentation_unet.py:670-845.  The reference passes it no normalisation arguments: it is
+    always LayerNorm2d + ReLU, with the submodule names (and state_dict keys) of the extended head.  Its aux dict has
+    no ``shared_features``.  Inference only: the eval-mode forward runs through :func:`hiseg.engine.hier_head`."""
+
+    def __init__(self, in_channels: int, mid_channels: int = 256, num_classes: int = 3,
+                 mask_size: Union[int, Tuple[int, int]] = 56, dropout_rate: float = 0.1,
+                 use_attention_module: bool = False, activation_function: str = "relu", activation_beta: float = 1.0,
+                 hierarchical_base_channels: int = 96, hierarchical_depth: int = 3):
+        # (activation_function / activation_beta are accepted and, as in the reference, not used: :714-773 are
+        # written with nn.ReLU and the blocks' defaults)
+        super().__init__(in_channels, mid_channels, num_classes, mask_size, dropout_rate, use_attention_module,
+                         normalization_type="layernorm2d", normalization_groups=8, activation_function="relu",
+                         activation_beta=1.0, hierarchical_base_channels=hierarchical_base_channels,
+                         hierarchical_depth=hierarchical_depth)
+
+    def forward(self, features: torch.Tensor):
+        if self.training:
+            raise NotImplementedError("HierarchicalSegmentationHeadUNetV2 is inference only on the hiseg path; "
+                                      "call .eval()")
+        return _engine().head_nchw(self, features)
+
+
+class RGBFeatureExtractor(nn.Module):
+    """3 -> 64 -> 128 -> 192 -> out_channels 3x3 convs at the ROI size, a residual block after every layer but the
+    first -- advanced/hierarchical_segmentation_rgb.py:221-295, quirks included: for a batchnorm type the block takes
+    the given normalisation and activation, for every other type it is the UNet module's ``ResidualBlock(out_ch)``
+    with its defaults (LayerNorm2d + ReLU).  The forward runs through :func:`hiseg.engine.rgb_extractor_plain`."""
+
+    def __init__(self, in_channels: int = 3, out_channels: int = 256, roi_size=28, num_layers: int = 4,
+                 normalization_type: str = "layernorm2d", normalization_groups: int = 8,
+                 activation_function: str = "relu", activation_beta: float = 1.0):
+        super().__init__()
+        self.roi_size = roi_size
+        norm, g, act, beta = normalization_type, normalization_groups, activation_function, activation_beta
+        channels = [in_channels, 64, 128, 192, out_channels][:num_layers + 1]
+        layers = []
+        for i in range(len(channels) - 1):
+            out_ch = channels[i + 1]
+            layers += [nn.Conv2d(channels[i], out_ch, 3, padding=1, stride=1), make_norm(norm, out_ch, g),
+                       make_act_unet(act, beta)]
+            if i >= 1:
+                if norm.lower() in ("batchnorm", "batchnorm2d"):
+                    layers.append(ResidualBlock(out_ch, norm, min(g, out_ch), act, beta, two_acts=False))
+                else:
+                    layers.append(ResidualBlock(out_ch, "layernorm2d", 8, "relu", 1.0, two_acts=False))
+        self.features = nn.Sequential(*layers)
+        self.output_size = roi_size
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        E = _engine()
+        E._check_input(x, "RGBFeatureExtractor")
+        ctx = E.Ctx(self, E._root_dtype(self), x.device)
+        return E.rgb_extractor_plain(ctx, self.features, E.Act.from_nchw(x, ctx.dtype)).to_nchw()
+
+
 class PretrainedUNetGuidedSegmentationHead(nn.Module):
     """Direct 3-class head guided by the full-image UNet's foreground logit --
     advanced/hierarchical_segmentation_rgb.py:43-218.  The model's head when no refinement flag is set (:715-727).

@@ -20,8 +20,8 @@ from . import engine
 from . import export
 from . import streams
 from .effunet import EfficientNetUnet
-from .layers import (PretrainedUNetGuidedSegmentationHead, RefinedHierarchicalSegmentationHead, ResidualBlock,
-                     make_act_unet, make_norm)
+from .layers import (HierarchicalSegmentationHeadUNetV2, PretrainedUNetGuidedSegmentationHead,
+                     RefinedHierarchicalSegmentationHead, ResidualBlock, RGBFeatureExtractor, make_act_unet, make_norm)
 
 
 class DynamicRoIAlign(nn.Module):
@@ -212,6 +212,78 @@ class HierarchicalRGBSegmentationModelWithFullImagePretrainedUNet(nn.Module):
         return logits, aux["unet_logit"]
 
 
+class HierarchicalRGBSegmentationModel(nn.Module):
+    """The plain RGB model: RoIAlign (aligned=False) of the image -> RGBFeatureExtractor -> hierarchical head.  No
+    full-image UNet and no feature combiner (advanced/hierarchical_segmentation_rgb.py:298-439).  The head is the
+    plain HierarchicalSegmentationHeadUNetV2 when no refinement flag is set, the refined head otherwise.  As in the
+    reference, only the normalisation reaches the extractor and the refined head; the activation is their default.
+    Inference only on the hiseg path."""
+
+    def __init__(self, roi_size: Union[int, Tuple[int, int]] = 28, mask_size: Union[int, Tuple[int, int]] = 56,
+                 feature_channels: int = 256, num_classes: int = 3, use_attention_module: bool = False,
+                 use_boundary_refinement: bool = False, use_progressive_upsampling: bool = False,
+                 use_subpixel_conv: bool = False, use_contour_detection: bool = False,
+                 use_distance_transform: bool = False, **kwargs):
+        super().__init__()
+        if isinstance(roi_size, (tuple, list)):
+            self.roi_height, self.roi_width = int(roi_size[0]), int(roi_size[1])
+            self.roi_size = roi_size[0]   # (as the reference keeps it, :336)
+        else:
+            self.roi_height = self.roi_width = self.roi_size = int(roi_size)
+        if isinstance(mask_size, (tuple, list)):
+            self.mask_height, self.mask_width = int(mask_size[0]), int(mask_size[1])
+        else:
+            self.mask_height = self.mask_width = int(mask_size)
+        self.mask_size = mask_size
+        norm = kwargs.get("normalization_type", "layernorm2d")
+        g = kwargs.get("normalization_groups", 8)
+        self.rgb_extractor = RGBFeatureExtractor(in_channels=3, out_channels=feature_channels, roi_size=roi_size,
+                                                 num_layers=4, normalization_type=norm, normalization_groups=g)
+        if any([use_boundary_refinement, use_progressive_upsampling, use_subpixel_conv, use_contour_detection,
+                use_distance_transform]):
+            self.segmentation_head = RefinedHierarchicalSegmentationHead(
+                in_channels=feature_channels, mid_channels=256, num_classes=num_classes, mask_size=mask_size,
+                use_attention_module=use_attention_module, use_boundary_refinement=use_boundary_refinement,
+                use_progressive_upsampling=use_progressive_upsampling, use_subpixel_conv=use_subpixel_conv,
+                use_contour_detection=use_contour_detection, use_distance_transform=use_distance_transform,
+                normalization_type=norm, normalization_groups=g)
+        else:
+            self.segmentation_head = HierarchicalSegmentationHeadUNetV2(
+                in_channels=feature_channels, mid_channels=256, num_classes=num_classes, mask_size=mask_size,
+                use_attention_module=use_attention_module)
+        # ROIs are normalised [0,1], images 640x640 (:404-408); serving code sets spatial_scale_h / _w to (H, W)
+        self.roi_align = DynamicRoIAlign(spatial_scale=640.0, sampling_ratio=2, aligned=False)
+        # compute precision of the HIP path (hiseg.set_compute_dtype): f32 (parity) or bf16 (throughput)
+        self.hiseg_dtype = torch.float32
+
+    def _refuse(self, images, rois):
+        if self.training:
+            raise NotImplementedError(
+                "HierarchicalRGBSegmentationModel is inference only on the hiseg path (training the plain RGB model "
+                "is not built); call model.eval()")
+        if export.tracing(images, rois):
+            raise NotImplementedError(
+                "traced / torch.export / ONNX export of the plain HierarchicalRGBSegmentationModel is not supported; "
+                "serve it with the eager path (model.infer)")
+
+    def forward(self, images: torch.Tensor, rois: torch.Tensor) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+        self._refuse(images, rois)
+        return engine.rgb_plain_forward(self, images, rois, aux="full")
+
+    def infer(self, images: torch.Tensor, rois: torch.Tensor) -> torch.Tensor:
+        """Logits [N,3,mh,mw], no aux tensors (serving path)."""
+        self._refuse(images, rois)
+        return engine.rgb_plain_forward(self, images, rois, aux="none")[0]
+
+
+def _refuse_plain(model, what: str):
+    if isinstance(model, HierarchicalRGBSegmentationModel):
+        raise NotImplementedError(
+            f"{what} wraps the full-image pretrained-UNet model: its contract returns the UNet's binary_masks, and "
+            "the plain HierarchicalRGBSegmentationModel has no UNet; call model.infer(images, rois) and "
+            "hiseg.ops.instance_masks")
+
+
 class RGBHierarchicalExportWrapper(nn.Module):
     """The exported ONNX contract (export_onnx_advanced.py:353-420, export_hierarchical_instance_peopleseg_onnx.py
     :85-181): images [B,3,H,W] in [0,1], rois [N,5] -> instance_masks [N,1,mh,mw], binary_masks [B,1,H,W].
@@ -233,6 +305,7 @@ class RGBHierarchicalExportWrapper(nn.Module):
     def __init__(self, model: HierarchicalRGBSegmentationModelWithFullImagePretrainedUNet, image_size=None,
                  dilation_pixels: int = 0, binary_post=None, instance_post=None, compose=None):
         super().__init__()
+        _refuse_plain(model, "RGBHierarchicalExportWrapper")
         self.model = model
         self.image_size = image_size
         self.dilation_pixels = dilation_pixels
@@ -289,6 +362,7 @@ class StreamPipelinedExport:
         critical path once the UNet got cheaper -- runs on a high-priority stream, so its workgroups are dispatched
         ahead of the UNet's when both wait for CUs (tools/pipeline_ab.py, profiles/r2_v11_schedule_ab2.txt: 19.0-19.3
         vs 19.5-19.7 ms per step on one box, 19.35-19.6 vs 19.8-20.0 on another)."""
+        _refuse_plain(getattr(wrapper, "model", wrapper), "StreamPipelinedExport")
         self.wrapper = wrapper
         self._raw_unet = None
         if unet_cu_mask is None:
@@ -488,7 +562,9 @@ def create_rgb_hierarchical_model(roi_size=28, mask_size=56, multi_scale: bool =
                                   activation_function: str = "relu", activation_beta: float = 1.0,
                                   normalization_type: str = "layernorm2d", normalization_groups: int = 8,
                                   **kwargs) -> nn.Module:
-    """Factory of advanced/hierarchical_segmentation_rgb.py:925-1027 (full-image pretrained-UNet branch)."""
+    """Factory of advanced/hierarchical_segmentation_rgb.py:925-1027: the full-image pretrained-UNet branch and the
+    plain RGB model (``use_pretrained_unet=False``, the default; as in the reference it is given the refinement flags
+    and the normalisation only)."""
     use_attention_module = kwargs.pop("use_attention_module", False)
     flags = {k: kwargs.pop(k, False) for k in ("use_boundary_refinement", "use_progressive_upsampling",
                                                "use_subpixel_conv", "use_contour_detection", "use_distance_transform")}
@@ -498,10 +574,14 @@ def create_rgb_hierarchical_model(roi_size=28, mask_size=56, multi_scale: bool =
     full_image = kwargs.pop("use_full_image_unet", False)
     kwargs.pop("roi_sizes", None)
     kwargs.pop("fusion_method", None)
-    if multi_scale or not (use_pretrained_unet and full_image):
+    if multi_scale or (use_pretrained_unet and not full_image):
         raise NotImplementedError(
-            "hiseg implements the full-image pretrained-UNet RGB hierarchical model (the BASELINE.json hot path); "
-            "multi-scale / ROI-UNet / plain RGB variants are out of scope (SURVEY.md §2.1)")
+            "hiseg implements the full-image pretrained-UNet RGB hierarchical model (the BASELINE.json hot path) and "
+            "the plain RGB model; the multi-scale and ROI-UNet variants are out of scope (SURVEY.md §2.1)")
+    if not use_pretrained_unet:
+        return HierarchicalRGBSegmentationModel(
+            roi_size=roi_size, mask_size=mask_size, use_attention_module=use_attention_module, **flags,
+            normalization_type=normalization_type, normalization_groups=normalization_groups)
     return HierarchicalRGBSegmentationModelWithFullImagePretrainedUNet(
         roi_size=roi_size, mask_size=mask_size, pretrained_weights_path=pretrained_weights_path,
         use_attention_module=use_attention_module, freeze_pretrained_weights=freeze,

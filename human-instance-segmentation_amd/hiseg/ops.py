@@ -709,6 +709,26 @@ def hier_combine(low: torch.Tensor, N: int, h: int, w: int, tfeat: Optional[Act]
     return logits, bgfg, tn
 
 
+def hier_combine_resize(low: torch.Tensor, N: int, h: int, w: int, tn2: torch.Tensor, ut_w, ut_scale, ut_shift, ut_act,
+                        u1_w, u1_b, mh: int, mw: int, want_aux: bool, per_sample: bool = False):
+    """hier_combine at a mask size (mh, mw) other than (2h, 2w): upsample_bg_fg, the bilinear resize of its two
+    logits and of the target logits ``tn2`` (f32 [N*2h*2w, 2]) to the mask size, the softmax and the combine in one
+    launch (hiseg_hier_combine_resize).  Returns logits [N,3,mh,mw] and, with ``want_aux``, the resized bg/fg and
+    target logits [N,2,mh,mw]."""
+    _require_gpu(low, tn2)
+    dev = low.device
+    assert tn2.dtype == torch.float32 and tn2.is_contiguous() and tn2.numel() == N * 4 * h * w * 2
+    logits = torch.empty(N, 3, mh, mw, dtype=torch.float32, device=dev)
+    bgfg = torch.empty(N, 2, mh, mw, dtype=torch.float32, device=dev) if want_aux else None
+    tn = torch.empty(N, 2, mh, mw, dtype=torch.float32, device=dev) if want_aux else None
+    L.check(L.lib().hiseg_hier_combine_resize(low.data_ptr(), N, h, w, tn2.data_ptr(), ut_w.data_ptr(),
+                                              ut_scale.data_ptr(), ut_shift.data_ptr(), int(ut_act),
+                                              L.act_beta(ut_act), int(per_sample), u1_w.data_ptr(), u1_b.data_ptr(),
+                                              int(mh), int(mw), logits.data_ptr(), _ptr(bgfg), _ptr(tn),
+                                              L.stream_ptr()), "hier_combine_resize")
+    return logits, bgfg, tn
+
+
 def layernorm2d(z: Act, weight: torch.Tensor, bias: torch.Tensor, eps: float, act: int,
                 residual: Optional[Act] = None, out: Optional[Act] = None) -> Act:
     """LayerNorm2d (model.py:18-38) of a conv output z, then (+ residual) and the activation:

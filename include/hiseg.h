@@ -339,6 +339,19 @@ int hiseg_hier_combine_tn_fwd(const float* low, int N, int h, int w, const float
                               const float* ut_scale, const float* ut_shift, int ut_act, float ut_beta,
                               int ut_per_sample, const float* u1_w, const float* u1_b, float* logits,
                               float* bgfg, float* tn, hiseg_stream_t stream);
+/* The combine at a mask size (mh, mw) other than (2h, 2w): the reference resizes the bg/fg logits
+ * and the target logits bilinearly (align_corners=False) from 2h x 2w to the mask size before the
+ * softmax and the combine (refinement.py:559-596, hierarchical_segmentation_unet.py:785-836).  One
+ * launch: upsample_bg_fg is evaluated once per pixel of each workgroup's 2h x 2w source window into
+ * LDS, the bg/fg logits never exist at 2h x 2w in memory.  Arguments as hiseg_hier_combine_tn_fwd
+ * (tn2 f32 [N*2h*2w][2], 8-byte aligned).  Outputs (f32 NCHW): logits [N,3,mh,mw]; optional bgfg
+ * [N,2,mh,mw], tn [N,2,mh,mw] -- the resized tensors.  Any (mh, mw) > 0 whose per-tile source
+ * window fits 48 KiB of LDS (every mask of at least a third of 2h x 2w per axis does);
+ * HISEG_ERR_BAD_SHAPE otherwise.  (mh, mw) = (2h, 2w) gives hiseg_hier_combine_tn_fwd's bits. */
+int hiseg_hier_combine_resize(const float* low, int N, int h, int w, const float* tn2, const float* ut_w,
+                              const float* ut_scale, const float* ut_shift, int ut_act, float ut_beta,
+                              int ut_per_sample, const float* u1_w, const float* u1_b, int mh, int mw,
+                              float* logits, float* bgfg, float* tn, hiseg_stream_t stream);
 /* upsample_bg_fg with LayerNorm2d (normalization_type 'layernorm2d', model.py:18-38): per-sample
  * statistics of z = ConvTranspose2d(low) (+ bias) over (32, 2h, 2w) -> mean/invstd [N] (optional)
  * and the folded tables scale/shift [N][32]: act(z * scale + shift) -- or, with fold_bias = 1, the
