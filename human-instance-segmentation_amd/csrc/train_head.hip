@@ -8,8 +8,7 @@
 // All are HBM-streaming kernels; reductions go through deterministic per-block partials and a
 // finalize kernel (no atomics).
 #include <float.h>
-#include "common.h"
-#include "hiseg_train.h"
+#include "train_norm.h"
 #include "hiseg_head_train.h"
 
 namespace hiseg {
@@ -934,22 +933,6 @@ __global__ void __launch_bounds__(256) pw2_bwd_kernel(const void* tfeat, long lo
 }  // namespace hiseg
 
 using namespace hiseg;
-
-#define DISPATCH_T(dtype, ...)        \
-  do {                                \
-    if ((dtype) == HISEG_BF16) {      \
-      using T = bf16_t;               \
-      __VA_ARGS__;                    \
-    } else {                          \
-      using T = float;                \
-      __VA_ARGS__;                    \
-    }                                 \
-  } while (0)
-
-// train_norm.hip: the BatchNorm statistics merge over an explicit split count
-int bn_finalize_splits(const float* partial, int S, int C, long long P, const float* gamma, const float* beta,
-                       float eps, float momentum, float* running_mean, float* running_var, float* mean, float* invstd,
-                       float* scale, float* shift, hipStream_t stream, long long rs = 0);
 
 extern "C" int hiseg_attn_spatial_train_fwd(int dtype, const void* x, int N, int H, int W, int C, const float* w7, int k,
                                             const float* chan_mul, float* stats, int* argmax, float* att, void* out,

@@ -498,7 +498,7 @@ def conv_bwd(T: Tape, p: TConv, d: L.Conv2dDesc, xa: Act, xb: Optional[Act], dz:
             dg.bnb_act = int(fb["act"])
             S_ = int(lib.hiseg_conv2d_stats_tiles(ctypes.byref(dg)))
             if S_ > 0:
-                part = torch.empty((S_ + (S_ + 63) // 64 + 1) * 3 * z.C, dtype=torch.float32, device=dz.t.device)
+                part = torch.empty(bn_bwd_partial_floats(z.C, S_), dtype=torch.float32, device=dz.t.device)
                 dg.bnb_partial = part
                 fb["part"], fb["S"] = part, S_
             else:
@@ -547,6 +547,47 @@ def _bn_module(bn):
     return bn
 
 
+def bn_stats_partial_floats(C: int) -> int:
+    """Floats of hiseg_bn_stats' partial buffer: at most hiseg_bn_partials() split rows of [3][C]."""
+    return L.lib().hiseg_bn_partials() * 3 * C
+
+
+def bn_bwd_partial_floats(C: int, pre_splits: int = 0) -> int:
+    """Floats of hiseg_bn_bwd's partial buffer: the split rows (``pre_splits`` of a data gradient's epilogue with their
+    group rows, one per 64) and the coefficient row."""
+    rows = pre_splits + (pre_splits + 63) // 64 if pre_splits else L.lib().hiseg_bn_partials()
+    return (rows + 1) * 3 * C
+
+
+def _norm_apply(z: Act, st, y: Act, act: int, residual: Optional[Act], drop, per_sample: int, what: str):
+    """y = act(z * st.scale + st.shift + residual) * drop (hiseg_bn_apply; per_sample: LayerNorm2d's [N][C] tables)."""
+    d = L.BnApplyDesc()
+    d.dtype, d.P, d.HW, d.C = hdtype(z.dtype), z.N * z.H * z.W, z.H * z.W, z.C
+    d.z, d.z_cstride, d.z_coff = z, z.cstride, z.coff
+    d.scale, d.shift, d.per_sample = st.scale, st.shift, per_sample
+    if residual is not None:
+        d.residual, d.r_cstride, d.r_coff = residual, residual.cstride, residual.coff
+    d.act, d.act_beta = int(act), L.act_beta(act)
+    d.chan_mul = (drop)
+    d.y, d.y_cstride, d.y_coff = y, y.cstride, y.coff
+    _chk(L.lib().hiseg_bn_apply(ctypes.byref(d), _stream()), what)
+
+
+def _norm_bwd_views(T: Tape, d, gy: Act, z: Act, dz: Act, act: int, drop, conv_bias, residual: Optional[Act]):
+    """The fields BnBwdDesc and LnBwdDesc share: dy / z / dz views, activation, mask, bias gradient and, last, the
+    residual's gradient (the residual itself is the caller's to set)."""
+    d.dtype, d.HW, d.C = hdtype(z.dtype), z.H * z.W, z.C
+    d.dy, d.dy_cstride, d.dy_coff = gy, gy.cstride, gy.coff
+    d.z, d.z_cstride, d.z_coff = z, z.cstride, z.coff
+    d.chan_mul, d.act, d.act_beta = (drop), int(act), L.act_beta(act)
+    d.dconv_bias = (conv_bias)
+    d.accumulate_params = 1
+    d.dz, d.dz_cstride, d.dz_coff = dz, dz.cstride, dz.coff
+    if residual is not None:
+        gr, acc = T.grad(residual)
+        d.dres, d.dres_cstride, d.dres_coff, d.dres_accumulate = gr, gr.cstride, gr.coff, int(acc)
+
+
 def ln_forward(T: Tape, ln: LayerNorm2d, z: Act, *, act: int, residual: Optional[Act] = None,
                drop: Optional[torch.Tensor] = None, out: Optional[Act] = None) -> Tuple[Act, LNState]:
     """LayerNorm2d (model.py:18-38): per-sample statistics of z over (C, H, W), y = act(ln(z) + residual) * drop."""
@@ -558,16 +599,7 @@ def ln_forward(T: Tape, ln: LayerNorm2d, z: Act, *, act: int, residual: Optional
                                 st.invstd.data_ptr(), st.scale.data_ptr(), st.shift.data_ptr(), _stream()),
          "ln_fwd_stats")
     y = out if out is not None else Act.new(N, z.H, z.W, C, z.dtype, z.t.device, cpad=z.cstride)
-    d = L.BnApplyDesc()
-    d.dtype, d.P, d.HW, d.C = hdtype(z.dtype), N * HW, HW, C
-    d.z, d.z_cstride, d.z_coff = z, z.cstride, z.coff
-    d.scale, d.shift, d.per_sample = st.scale, st.shift, 1
-    if residual is not None:
-        d.residual, d.r_cstride, d.r_coff = residual, residual.cstride, residual.coff
-    d.act, d.act_beta = int(act), L.act_beta(act)
-    d.chan_mul = (drop)
-    d.y, d.y_cstride, d.y_coff = y, y.cstride, y.coff
-    _chk(lib.hiseg_bn_apply(ctypes.byref(d), _stream()), "ln_apply")
+    _norm_apply(z, st, y, act, residual, drop, 1, "ln_apply")
     return y, st
 
 
@@ -576,23 +608,13 @@ def ln_backward(T: Tape, ln: LayerNorm2d, z: Act, y: Act, st: LNState, dz: Act, 
     lib, S = L.lib(), T.S
     gy = T.grad_in(y)
     d = L.LnBwdDesc()
-    d.dtype, d.N, d.HW, d.C = hdtype(z.dtype), z.N, z.H * z.W, z.C
-    d.dy, d.dy_cstride, d.dy_coff = gy, gy.cstride, gy.coff
-    d.z, d.z_cstride, d.z_coff = z, z.cstride, z.coff
-    d.chan_mul, d.act, d.act_beta = (drop), int(act), L.act_beta(act)
-    d.mean, d.invstd, d.scale, d.shift = st.mean, st.invstd, st.scale, \
-        st.shift
-    d.gamma = ln.weight
+    d.N, d.ws, d.gamma = z.N, st.ws, ln.weight
+    d.mean, d.invstd, d.scale, d.shift = st.mean, st.invstd, st.scale, st.shift
     d.dgamma = (S.grad(ln.weight)) if ln.weight.requires_grad else None
     d.dbeta = (S.grad(ln.bias)) if ln.bias.requires_grad else None
-    d.dconv_bias = (conv_bias)
-    d.accumulate_params = 1
-    d.dz, d.dz_cstride, d.dz_coff = dz, dz.cstride, dz.coff
-    d.ws = st.ws
     if residual is not None:
-        gr, acc = T.grad(residual)
         d.residual, d.r_cstride, d.r_coff = residual, residual.cstride, residual.coff
-        d.dres, d.dres_cstride, d.dres_coff, d.dres_accumulate = gr, gr.cstride, gr.coff, int(acc)
+    _norm_bwd_views(T, d, gy, z, dz, act, drop, conv_bias, residual)
     _chk(lib.hiseg_ln_bwd(ctypes.byref(d), _stream()), "ln_bwd")
     if residual is not None:
         T.mark(residual)
@@ -612,7 +634,7 @@ def bn_forward(T: Tape, bn: nn.BatchNorm2d, z: Act, *, act: int, residual: Optio
     if stats:
         part, splits = stats
     else:
-        part, splits = torch.empty(lib.hiseg_bn_partials() * 3 * C, dtype=torch.float32, device=z.t.device), None
+        part, splits = torch.empty(bn_stats_partial_floats(C), dtype=torch.float32, device=z.t.device), None
         _chk(lib.hiseg_bn_stats(hdtype(z.dtype), z.ptr(), P, C, z.cstride, z.coff, part.data_ptr(), _stream()),
              "bn_stats")
     track = bn.track_running_stats and bn.running_mean is not None
@@ -629,16 +651,7 @@ def bn_forward(T: Tape, bn: nn.BatchNorm2d, z: Act, *, act: int, residual: Optio
     if track:   # the kernel updated the running statistics in place: invalidate eval plans folded from them
         torch.autograd.graph.increment_version([bn.running_mean, bn.running_var])
     y = out if out is not None else Act.new(z.N, z.H, z.W, C, z.dtype, z.t.device, cpad=z.cstride)
-    d = L.BnApplyDesc()
-    d.dtype, d.P, d.HW, d.C = hdtype(z.dtype), P, z.H * z.W, C
-    d.z, d.z_cstride, d.z_coff = z, z.cstride, z.coff
-    d.scale, d.shift = st.scale, st.shift
-    if residual is not None:
-        d.residual, d.r_cstride, d.r_coff = residual, residual.cstride, residual.coff
-    d.act, d.act_beta = int(act), L.act_beta(act)
-    d.chan_mul = (drop)
-    d.y, d.y_cstride, d.y_coff = y, y.cstride, y.coff
-    _chk(lib.hiseg_bn_apply(ctypes.byref(d), _stream()), "bn_apply")
+    _norm_apply(z, st, y, act, residual, drop, 0, "bn_apply")
     return y, st
 
 
@@ -648,33 +661,20 @@ def bn_backward(T: Tape, bn: nn.BatchNorm2d, z: Act, y: Act, st: BNState, dz: Ac
         return ln_backward(T, bn, z, y, st, dz, act=act, residual=residual, drop=drop, conv_bias=conv_bias)
     lib, S = L.lib(), T.S
     gy = T.grad_in(y)
-    C = z.C
-    P = z.N * z.H * z.W
     fb = T.bnb.pop(id(y), None)
     if fb is not None and fb["part"] is not None:   # the data gradient's epilogue did the reduction
         part, pre_splits = fb["part"], fb["S"]
         FUSED_BN_BWD_TAKEN[0] += 1
     else:
-        part, pre_splits = torch.empty((lib.hiseg_bn_partials() + 1) * 3 * C, dtype=torch.float32,
-                                       device=z.t.device), 0
+        part, pre_splits = torch.empty(bn_bwd_partial_floats(z.C), dtype=torch.float32, device=z.t.device), 0
     d = L.BnBwdDesc()
-    d.partial_splits = pre_splits
-    d.dtype, d.P, d.HW, d.C = hdtype(z.dtype), P, z.H * z.W, C
-    d.dy, d.dy_cstride, d.dy_coff = gy, gy.cstride, gy.coff
+    d.partial, d.partial_splits, d.P = part, pre_splits, z.N * z.H * z.W
     d.y, d.y_cstride, d.y_coff = y, y.cstride, y.coff
-    d.z, d.z_cstride, d.z_coff = z, z.cstride, z.coff
-    d.chan_mul, d.act, d.act_beta = (drop), int(act), L.act_beta(act)
     d.mean, d.invstd, d.gamma, d.beta = st.mean, st.invstd, (bn.weight), (bn.bias)
-    d.partial = part
     d.dgamma = (S.grad(bn.weight)) if bn.weight is not None and bn.weight.requires_grad else None
     d.dbeta = (S.grad(bn.bias)) if bn.bias is not None and bn.bias.requires_grad else None
-    d.dconv_bias = (conv_bias)
-    d.accumulate_params = 1
-    d.dz, d.dz_cstride, d.dz_coff = dz, dz.cstride, dz.coff
-    if residual is not None:
-        gr, acc = T.grad(residual)
-        d.dres, d.dres_cstride, d.dres_coff, d.dres_accumulate = gr, gr.cstride, gr.coff, int(acc)
-    elif act == ACT_RELU:   # ReLU mask recomputed from z with the forward's folded affine: y is not re-read
+    _norm_bwd_views(T, d, gy, z, dz, act, drop, conv_bias, residual)
+    if residual is None and act == ACT_RELU:   # mask from z and the forward's folded affine: y is not re-read
         d.fwd_scale, d.fwd_shift = st.scale, st.shift
     if int(act) in (ACT_GELU, ACT_SWISH) or (int(act) == ACT_SILU and residual is not None):
         # derivative at the forward's own pre-activation z*scale + shift (+ residual)

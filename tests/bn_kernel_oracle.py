@@ -1,6 +1,6 @@
 """Plain torch restatement of train-mode BatchNorm as include/hiseg_train.h declares it: hiseg_bn_stats,
 hiseg_bn_finalize / _finalize_n, hiseg_bn_apply and hiseg_bn_bwd.  Written from the header's formulas, not from
-csrc/train_norm.hip.
+csrc/bn_train.hip.
 
 Every function is dtype-generic (it computes in the dtype of its floating inputs), so the GPU tests evaluate each
 one in float64 -- the reference -- and in float32, whose distance from the float64 result (`e32`) is the yardstick

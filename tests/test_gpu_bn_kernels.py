@@ -60,7 +60,7 @@ Worst observed ratio of kernel error over bound per kernel and dtype (profiles/b
 HISEG_BN_U=2 against U = 1 is compared bit for bit (bn_apply; bn_bwd's dz, dres and parameter gradients).  The
 comparison found the f32 backward's dz one rounding apart for sigmoid / SiLU / GELU / Swish: the U = 1 instance fused
 g's last multiply into g - sum(g)/P, the U = 2 instance, whose g is computed in its load loop, could not.  g's
-products are now rounded explicitly (mul_rounded in csrc/train_norm.hip), so every instance builds dz from the g that
+products are now rounded explicitly (mul_rounded in csrc/bn_train.hip), so every instance builds dz from the g that
 dres stores.
 """
 import math
@@ -72,6 +72,7 @@ import torch
 
 import bn_kernel_oracle as B
 from hiseg import _lib as L
+from hiseg import train_engine as TE
 
 pytestmark = pytest.mark.gpu
 
@@ -85,6 +86,7 @@ EPS, MOM = 1e-5, 0.1
 EPS32 = float(torch.tensor(EPS, dtype=torch.float32))
 MOM32 = float(torch.tensor(MOM, dtype=torch.float32))
 BAD_ARG = -1
+KPRE = 64                # csrc/bn_train.hip, constexpr int KPRE: given split rows are summed in groups of KPRE above 4 KPRE
 RATIOS = {}
 NONE, RELU, SIGMOID, SILU, GELU, SWISH = range(6)
 
@@ -167,17 +169,23 @@ class View:
 
 
 class F32:
-    """n f32 values (the sentinel if vals is None) followed by a guard tail."""
+    """n f32 values (`fill`, the sentinel by default, if vals is None) followed by a guard tail of the sentinel."""
 
-    def __init__(self, vals=None, n=None):
+    def __init__(self, vals=None, n=None, fill=SENTINEL):
         n = vals.numel() if vals is not None else n
         flat = torch.full((n + GUARD,), SENTINEL, dtype=torch.float32)
+        flat[:n] = fill
         if vals is not None:
             flat[:n] = vals.reshape(-1).float()
         self.n, self.t = n, flat.to(DEV)
 
     def get(self, *shape):
         return self.t[:self.n].double().cpu().reshape(*shape) if shape else self.t[:self.n].double().cpu()
+
+    def assert_written(self, floats):
+        """A buffer filled with NaN: exactly its first `floats` values were written."""
+        live = ~torch.isnan(self.t[:self.n])
+        assert int(live.sum()) == floats and bool(live[:floats].all()), (int(live.sum()), floats)
 
     def assert_tail(self, written=None):
         w = self.n if written is None else written
@@ -538,10 +546,10 @@ def test_apply(dt, C, layout, res_layout, per_sample, monkeypatch):
 
 @pytest.mark.parametrize("dt", list(DTYPES))
 def test_apply_scalar_grid_stride(dt):
-    """The scalar kernel's grid is capped (ew_blocks in csrc/train_norm.hip, read from the source: blocks of 256
+    """The scalar kernel's grid is capped (ew_blocks in csrc/train_norm.h, read from the source: blocks of 256
     elements): with one pixel more than cap * 256 / C the first threads take a second iteration.  C = 7 in rows of 8
     keeps the largest buffer near 10 MB."""
-    src = open(os.path.join(os.path.dirname(L.__file__), "..", "csrc", "train_norm.hip")).read()
+    src = open(os.path.join(os.path.dirname(L.__file__), "..", "csrc", "train_norm.h")).read()
     m = re.search(r"inline unsigned ew_blocks\(long long n\) \{.*?b > (\d+) \? (\d+) :", src, flags=re.S)
     assert m and m.group(1) == m.group(2), "ew_blocks no longer has the form this test reads its cap from"
     cap = int(m.group(1))
@@ -887,14 +895,13 @@ def test_finalize_n_scratch_contract(S):
         check_stat("bn_finalize_n", "f32", f"{name} S={S}", got[name], r[i], r[i], slack[name])
 
 
-@pytest.mark.parametrize("dt", list(DTYPES))
-@pytest.mark.parametrize("S", [40, 300])
-def test_bwd_partial_splits(dt, S):
-    """partial_splits > 0: `partial` already holds [S][3][C] sums of (g, g xhat, xhat), here summed by the test from
-    the oracle's per-pixel terms and rounded to f32; the reduction pass is skipped and above 256 splits the groups of
-    64 are summed first (f32: 16 sequential additions and a two-level tree, k = (16 + 2 + 4) / 2 on sum |rows|).  The
-    workspace is exactly (S + ceil(S / 64) + 1) * 3 * C floats."""
-    N, HW, C = 3, 37, 16
+BWD_GIVEN_C = 16
+
+
+def bwd_given_partials(dt, S, floats, fill):
+    """hiseg_bn_bwd on S split rows written by the test into a `partial` of `floats` values (`fill` elsewhere), checked
+    against float64; returns the buffer."""
+    N, HW, C = 3, 37, BWD_GIVEN_C
     P = N * HW
     inp = make_bwd_inputs(dt, N, HW, C, RELU, 1.0, True, True, True, True, True, 900 + S)
     args = (inp["dy"], inp["z"], inp["mean"], inp["invstd"], inp["gamma"], inp["beta"], RELU, 1.0, inp["mul"], HW)
@@ -906,8 +913,7 @@ def test_bwd_partial_splits(dt, S):
         rows[p % S, 1] += g64[p] * xh[p]
         rows[p % S, 2] += xh[p]
     rows = rows.float().double()
-    G = -(-S // 64)
-    part = F32(n=(S + G + 1) * 3 * C)
+    part = F32(n=floats, fill=fill)
     part.t[:S * 3 * C] = rows.reshape(-1).float().to(DEV)
     v = dict(dy=View(inp["dy"], dt), z=View(inp["z"], dt), dz=View(None, dt, "vec", P, C),
              residual=View(inp["res"], dt), dres=View(None, dt, "vec", P, C))
@@ -942,3 +948,70 @@ def test_bwd_partial_splits(dt, S):
                kk * (2 * b[0] + s[2] * b[1] / P + s[1] * b[2] / P) + U23 * r64[3].abs())
     for k in ("dgamma", "dbeta", "dconv_bias"):
         tabs[k].assert_tail()
+    return part
+
+
+@pytest.mark.parametrize("dt", list(DTYPES))
+@pytest.mark.parametrize("S", [40, 300])
+def test_bwd_partial_splits(dt, S):
+    """partial_splits > 0: `partial` already holds [S][3][C] sums of (g, g xhat, xhat), here summed by the test from
+    the oracle's per-pixel terms and rounded to f32; the reduction pass is skipped and above 256 splits the groups of
+    64 are summed first (f32: 16 sequential additions and a two-level tree, k = (16 + 2 + 4) / 2 on sum |rows|).  The
+    workspace is exactly (S + ceil(S / 64) + 1) * 3 * C floats."""
+    bwd_given_partials(dt, S, (S + -(-S // 64) + 1) * 3 * BWD_GIVEN_C, SENTINEL)
+
+
+# ------------------------------------------------------------------------------------------- partial buffer sizes
+# hiseg.train_engine sizes every `partial` it allocates with bn_stats_partial_floats / bn_bwd_partial_floats; the
+# kernels' write extent follows from the split count, KPRE and the 4 KPRE threshold in csrc/bn_train.hip.  Buffers of
+# exactly those sizes, filled with NaN, with the sentinel guard behind them.
+@pytest.mark.parametrize("dt", list(DTYPES))
+@pytest.mark.parametrize("S", [4 * KPRE, 4 * KPRE + 1])
+def test_bwd_partial_splits_threshold(dt, S):
+    """The last split count without a pre-merge and the first with one (G = 5 groups), the buffer sized as the engine
+    sizes the data-gradient epilogue's: the given rows, without a pre-merge one coefficient row, with one G group rows
+    and the coefficient row after them are all that is written, and the guard holds (bwd_given_partials)."""
+    G = -(-S // KPRE) if S > 4 * KPRE else 0
+    assert G == (5 if S == 4 * KPRE + 1 else 0)
+    part = bwd_given_partials(dt, S, TE.bn_bwd_partial_floats(BWD_GIVEN_C, S), float("nan"))
+    part.assert_written((S + G + 1) * 3 * BWD_GIVEN_C)
+
+
+# one split; hiseg_bn_partials() splits, the cap; 33 splits of 32 or 33 pixels
+EXTENT_P = [31, 32 * 1024, 33 * 32 + 5]
+
+
+@pytest.mark.parametrize("dt", list(DTYPES))
+@pytest.mark.parametrize("C", [8, 6])
+@pytest.mark.parametrize("P", EXTENT_P)
+def test_partial_buffer_extent(dt, C, P):
+    """hiseg_bn_stats writes exactly S * 3 * C floats of a bn_stats_partial_floats(C) buffer and hiseg_bn_bwd
+    (S + 1) * 3 * C of a bn_bwd_partial_floats(C) one (S rows of sums, one of coefficients), S = P // 32 clamped to
+    [1, hiseg_bn_partials()]; the guards hold and no output is NaN.  C = 8: the chunk kernels, C = 6: the scalar ones."""
+    cap = lib().hiseg_bn_partials()
+    assert EXTENT_P[1] == 32 * cap
+    S = max(1, min(cap, P // 32))
+    vec = C == 8
+    inp = make_bwd_inputs(dt, 1, P, C, NONE, 1.0, False, False, False, True, True, 1200 + C)
+    v = dict(dy=View(inp["dy"], dt), z=View(inp["z"], dt), dz=View(None, dt, "vec", P, C))
+    part = F32(n=TE.bn_stats_partial_floats(C), fill=float("nan"))
+    ok(lib().hiseg_bn_stats(HD[dt], v["z"].t.data_ptr(), P, C, v["z"].cstride, v["z"].coff, part.t.data_ptr(),
+                            stream()), "bn_stats")
+    path(entry="stats", vec=vec)
+    part.assert_tail()
+    part.assert_written(S * 3 * C)
+    assert part.get()[:S * 3 * C].reshape(S, 3, C)[:, 0].sum(0).eq(P).all(), "n does not sum to P"
+
+    part = F32(n=TE.bn_bwd_partial_floats(C), fill=float("nan"))
+    tabs = {k: F32(inp[k]) for k in ("mean", "invstd", "gamma", "beta")}
+    for k in ("dgamma", "dbeta", "dconv_bias"):
+        tabs[k] = F32(n=C)
+    ok(lib().hiseg_bn_bwd(bwd_desc(dt, P, P, C, v, tabs, NONE, 1.0, 0, 0, part), stream()), "bn_bwd")
+    path(entry="bwd", vec=vec, mode="none", reduce=True, premerge=False, par=True, u2=False)
+    part.assert_tail()
+    part.assert_written((S + 1) * 3 * C)
+    v["dz"].assert_rest_untouched()
+    assert not torch.isnan(v["dz"].live()).any()
+    for k in ("dgamma", "dbeta", "dconv_bias"):
+        tabs[k].assert_tail()
+        assert not torch.isnan(tabs[k].get()).any(), k
