@@ -734,7 +734,7 @@ extern "C" int hiseg_bn_finalize(const float* partial, int C, long long P, const
   return hiseg_check_launch("bn_finalize");
 }
 
-// The same merge over an explicit split count (the fused upsample_bg_fg statistics, train_head.hip: 1 024 splits).
+// The same merge over an explicit split count (the fused upsample_bg_fg statistics, ubf_train.hip: 1 024 splits).
 int bn_finalize_splits(const float* partial, int S, int C, long long P, const float* gamma, const float* beta,
                        float eps, float momentum, float* running_mean, float* running_var, float* mean, float* invstd,
                        float* scale, float* shift, hipStream_t stream, long long rs) {

@@ -145,6 +145,9 @@ template <> struct Chunk<bf16_t> {
 inline int chunk_of(int dtype) { return dtype == HISEG_BF16 ? 8 : 4; }
 inline unsigned nblocks(long long n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
+// misc.hip: att[p] = sigmoid(k x k correlation of stats[p] = (mean, max)), for inference and attn_spatial_train.hip
+void attn_map_launch(const float* stats, int N, int H, int W, const float* w7, int k, float* att, hipStream_t s);
+
 }  // namespace hiseg
 
 // Host-side error plumbing (defined in capi.cpp).

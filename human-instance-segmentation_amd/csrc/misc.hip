@@ -90,6 +90,11 @@ __global__ void __launch_bounds__(256) attn_map_kernel(const float* stats, int N
   att[gid] = sigmoidf_(acc);
 }
 
+void attn_map_launch(const float* stats, int N, int H, int W, const float* w7, int k, float* att, hipStream_t s) {
+  hipLaunchKernelGGL(attn_map_kernel, dim3(nblocks((long long)N * H * W, 256)), dim3(256), 0, s, stats, N, H, W, w7, k,
+                     att);
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256) pixel_scale_kernel(const void* x, long long P, int C, const float* att, void* out) {
   constexpr int K = Chunk<T>::N;
@@ -360,7 +365,7 @@ extern "C" int hiseg_attn_spatial_fwd(int dtype, const void* x, int N, int H, in
   hipStream_t s = (hipStream_t)stream;
   const long long P = (long long)N * H * W;
   DISPATCH_T(dtype, attn_stats_kernel, dim3(nblocks(P * 16, 256)), dim3(256), 0, s, x, P, C, stats);
-  hipLaunchKernelGGL(attn_map_kernel, dim3(nblocks(P, 256)), dim3(256), 0, s, stats, N, H, W, w7, k, att);
+  attn_map_launch(stats, N, H, W, w7, k, att, s);
   const long long tot = P * (C / chunk_of(dtype));
   DISPATCH_T(dtype, pixel_scale_kernel, dim3(nblocks(tot, 256)), dim3(256), 0, s, x, P, C, att, out);
   return hiseg_check_launch("attn_spatial");
@@ -374,7 +379,7 @@ extern "C" int hiseg_attn_map_fwd(int dtype, const void* x, int N, int H, int W,
   hipStream_t s = (hipStream_t)stream;
   const long long P = (long long)N * H * W;
   DISPATCH_T(dtype, attn_stats_kernel, dim3(nblocks(P * 16, 256)), dim3(256), 0, s, x, P, C, stats);
-  hipLaunchKernelGGL(attn_map_kernel, dim3(nblocks(P, 256)), dim3(256), 0, s, stats, N, H, W, w7, k, att);
+  attn_map_launch(stats, N, H, W, w7, k, att, s);
   return hiseg_check_launch("attn_map");
 }
 

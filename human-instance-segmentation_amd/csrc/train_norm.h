@@ -1,5 +1,6 @@
 // What bn_train.hip, ln_train.hip and train_ew.hip share (each piece is used by at least two of them), the type
-// dispatch they share with train_head.hip, and the one declaration of bn_finalize_splits.
+// dispatch they share with the head's training files (attn_spatial_train.hip, channel_gate_train.hip, ubf_train.hip),
+// and the one declaration each of bn_finalize_splits and sum_rows.
 #pragma once
 #include "common.h"
 #include "hiseg_train.h"
@@ -68,3 +69,6 @@ inline dim3 vec_grid(long long P, int C, int dtype) {
 int bn_finalize_splits(const float* partial, int S, int C, long long P, const float* gamma, const float* beta,
                        float eps, float momentum, float* running_mean, float* running_var, float* mean, float* invstd,
                        float* scale, float* shift, hipStream_t stream, long long rs = 0);
+
+// ubf_train.hip: out[c] (+)= sum_r part[r*ld + c], c < cols.  Consumes part (scratch) when rows > 64.
+namespace hiseg { void sum_rows(float* part, int rows, int ld, int cols, float* out, int acc, hipStream_t s); }

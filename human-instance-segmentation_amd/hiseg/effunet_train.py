@@ -144,16 +144,13 @@ def se_train(T: TE.Tape, se: nn.Module, h: Act) -> Act:
 
     def back():
         gout = T.grad_in(out)
-        gh, acc = T.grad(h)
-        target = gh if not acc else Act.new(h.N, h.H, h.W, C, h.dtype, dev, zero=False)
+        target = T.grad_target(h)
         ws2 = torch.empty_like(ws)
         TE._chk(lib.hiseg_se_train_bwd(hdtype(h.dtype), h.ptr(), N, HW, C, w1.data_ptr(), rd, w2.data_ptr(), ACT_SILU,
                                        gap.data_ptr(), hpre.data_ptr(), gate.data_ptr(), gout.ptr(), target.ptr(),
                                        ws2.data_ptr(), S.grad(w1).data_ptr(), S.grad(b1).data_ptr(),
                                        S.grad(w2).data_ptr(), S.grad(b2).data_ptr(), TE._stream()), "se_train_bwd")
-        if acc:
-            TE._chk(lib.hiseg_add_inplace(hdtype(h.dtype), h.N * HW, C, TE.ew(gh), TE.ew(target), TE._stream()), "add")
-        T.mark(h)
+        T.grad_done(h, target)
     T.push(back)
     return out
 

@@ -331,6 +331,17 @@ class Tape:
     def mark(self, a: Act):
         self.written[id(a)] = True
 
+    def grad_target(self, a: Act) -> Act:
+        """Where an overwriting backward puts a's gradient: its buffer, or once written a fresh one for grad_done."""
+        g, acc = self.grad(a)
+        return Act.new(a.N, a.H, a.W, a.C, a.dtype, a.t.device, zero=False) if acc else g
+
+    def grad_done(self, a: Act, target: Act):
+        g = self.grads[id(a)]
+        if target is not g:
+            _chk(L.lib().hiseg_add_inplace(hdtype(a.dtype), a.N * a.H * a.W, a.C, ew(g), ew(target), _stream()), "add")
+        self.mark(a)
+
     def has(self, a: Act) -> bool:
         return self.written.get(id(a), False)
 
@@ -942,15 +953,12 @@ def spatial_attention(T: Tape, m: nn.Module, x: Act, drop) -> Act:
 
     def back():
         gy = T.grad_in(out)
-        gx, acc = T.grad(x)
         ws = torch.empty(lib.hiseg_attn_spatial_ws(x.N, x.H, x.W, k), dtype=torch.float32, device=dev)
-        target = gx if not acc else Act.new(x.N, x.H, x.W, x.C, x.dtype, dev, zero=False)
+        target = T.grad_target(x)
         _chk(lib.hiseg_attn_spatial_bwd(hdtype(x.dtype), x.ptr(), x.N, x.H, x.W, x.C, w7.data_ptr(), k, _ptr(drop),
                                         stats.data_ptr(), amax.data_ptr(), att.data_ptr(), gy.ptr(), target.ptr(),
                                         ws.data_ptr(), S.grad(w7).data_ptr(), _stream()), "attn_spatial_bwd")
-        if acc:
-            _chk(lib.hiseg_add_inplace(hdtype(x.dtype), P, x.C, ew(gx), ew(target), _stream()), "add")
-        T.mark(x)
+        T.grad_done(x, target)
     T.push(back)
     return out
 
@@ -973,15 +981,12 @@ def channel_attention(T: Tape, m: nn.Module, x: Act, drop) -> Act:
 
     def back():
         gy = T.grad_in(out)
-        gx, acc = T.grad(x)
-        target = gx if not acc else Act.new(x.N, x.H, x.W, C, x.dtype, dev, zero=False)
+        target = T.grad_target(x)
         _chk(lib.hiseg_attn_channel_bwd(hdtype(x.dtype), x.ptr(), x.N, HW, C, w1.data_ptr(), Cr, w2.data_ptr(),
                                         int(act), L.act_beta(act), _ptr(drop), gap.data_ptr(), hpre.data_ptr(), g.data_ptr(), gy.ptr(),
                                         target.ptr(), ws.data_ptr(), S.grad(w1).data_ptr(), S.grad(w2).data_ptr(),
                                         _stream()), "attn_channel_bwd")
-        if acc:
-            _chk(lib.hiseg_add_inplace(hdtype(x.dtype), x.N * HW, C, ew(gx), ew(target), _stream()), "add")
-        T.mark(x)
+        T.grad_done(x, target)
     T.push(back)
     return out
 

@@ -135,6 +135,21 @@ def test_conv_splitk_workspace_plan_is_batch_invariant():
     assert ws(4, 16, 12, 64, 64, gated=False, k=3) == 0   # short K
 
 
+def test_head_training_workspace_sizes():
+    """hiseg_attn_channel_ws, hiseg_se_train_ws and hiseg_ubf_ws (no GPU call) keep their sizes, in floats."""
+    from hiseg import _lib as L
+    lib = L.lib()
+    for N, C, Cr in ((1, 8, 1), (3, 16, 2), (4, 1152, 48)):
+        attn = N * 64 * C + N * C + N * 2 * C * Cr   # pool partials of 64 splits, dgap, per-image weight gradients
+        assert lib.hiseg_attn_channel_ws(N, C, Cr) == attn, (N, C, Cr)
+        assert lib.hiseg_se_train_ws(N, C, Cr) == attn + N * (Cr + C), (N, C, Cr)   # + the (dh, ds) rows
+    for N in (1, 2, 64, 4096):
+        # backward: block partials (pass 1: N * max(2048 // N, 1) rows of 162; pass 2: 2048 rows of 256), coef [96],
+        # coef_ln [N][2], dbias [N][32]; forward: the BatchNorm statistics' split rows of [3][32]
+        part = max(N * max(2048 // N, 1) * 162, 2048 * 256)
+        assert lib.hiseg_ubf_ws(N) == max(part + 96 + 34 * N, lib.hiseg_bn_partials() * 96), N
+
+
 def test_descriptor_holds_plain_tensors_and_activation_views():
     """A pointer field assigned a torch.Tensor stores its address and keeps it alive (torch.Tensor has a .t method,
     which must not be mistaken for an activation view's .t); an object that is neither raises; strict mode refuses

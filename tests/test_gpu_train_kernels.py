@@ -19,7 +19,8 @@ Entry point -> test
   hiseg_maxpool2x2_bwd                    test_maxpool2x2_bwd
   hiseg_upsample2x_bwd                    test_upsample2x_bwd, test_upsample2x_bwd_rejects_misaligned_view
   hiseg_resize_bilinear_bwd (and _fwd)    test_resize_bilinear_bwd
-  hiseg_attn_spatial_train_fwd / _bwd     test_spatial_attention, test_spatial_attention_tied_maximum
+  hiseg_attn_spatial_train_fwd / _bwd     test_spatial_attention, test_spatial_attention_tied_maximum,
+                                          test_spatial_attention_sum_rows_threshold
   hiseg_attn_channel_train_fwd / _bwd     test_channel_attention
   hiseg_se_train_fwd / _bwd               test_squeeze_excite
   hiseg_ubf_train_fwd / _bwd              test_ubf_head
@@ -27,6 +28,8 @@ Entry point -> test
   hiseg_roi_align_bwd_affine              test_roi_align_bwd_affine
   hiseg_ln_fwd_stats, hiseg_ln_bwd        test_layernorm2d
   hiseg_dropout2d_mask / _dev, hiseg_seed_advance   test_dropout_masks
+  hiseg_attn_spatial_ws, hiseg_attn_channel_ws, hiseg_se_train_ws, hiseg_ubf_ws, hiseg_pw2_ws
+                                          test_workspace_extents (the sizes themselves: tests/test_abi.py, no GPU)
 
 Worst observed ratio of kernel error over bound per kernel and dtype (profiles/train_kernel_errors.txt):
 
@@ -59,6 +62,7 @@ Worst observed ratio of kernel error over bound per kernel and dtype (profiles/t
 """
 import ctypes
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -127,6 +131,31 @@ def up(t, dtype=torch.float32):
 
 def ptr(t):
     return None if t is None else t.data_ptr()
+
+
+def workspace(n):
+    """A kernel's float workspace of the size its *_ws entry point gave (test_workspace_extents guards it)."""
+    return torch.empty(n, device=DEV)
+
+
+class GuardedWorkspaces:
+    """workspace() with NaN contents and 64 sentinel floats behind each buffer."""
+    GUARD = 64
+
+    def __init__(self):
+        self.bufs = []
+
+    def __call__(self, n):
+        buf = torch.full((n + self.GUARD,), float("nan"), device=DEV)
+        buf[n:] = SENTINEL
+        self.bufs.append(buf)
+        return buf[:n]
+
+    def assert_guards_untouched(self):
+        assert self.bufs, "no workspace was allocated"
+        want = torch.full((self.GUARD,), SENTINEL, device=DEV).view(torch.int32)
+        for buf in self.bufs:
+            assert torch.equal(buf[-self.GUARD:].view(torch.int32), want), "a kernel wrote past its workspace"
 
 
 class View:
@@ -455,7 +484,7 @@ def run_spatial(dt, x, w7, mul, dout, dw_old):
     out, dx = torch.empty_like(xd), torch.empty_like(xd)
     ok(lib().hiseg_attn_spatial_train_fwd(HD[dt], ptr(xd), N, H, W, C, ptr(wd), k, ptr(md), ptr(stats), ptr(am),
                                           ptr(att), ptr(out), stream()), "attn_spatial_train_fwd")
-    ws = torch.empty(lib().hiseg_attn_spatial_ws(N, H, W, k), device=DEV)
+    ws = workspace(lib().hiseg_attn_spatial_ws(N, H, W, k))
     dw = up(dw_old)
     ok(lib().hiseg_attn_spatial_bwd(HD[dt], ptr(xd), N, H, W, C, ptr(wd), k, ptr(md), ptr(stats), ptr(am), ptr(att),
                                     ptr(dd), ptr(dx), ptr(ws), ptr(dw), stream()), "attn_spatial_bwd")
@@ -502,6 +531,18 @@ def test_spatial_attention_tied_maximum():
     check_spatial("bf16", "tied", x, w7, None, dout, dw_old, run_spatial("bf16", x, w7, None, dout, dw_old))
 
 
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("H", [64, 65])
+def test_spatial_attention_sum_rows_threshold(dt, H):
+    """dw7 is summed over N * H partial rows by sum_rows: 64 rows take its single kernel, 65 the split path (R = 64,
+    S = 2) with a last split of one row."""
+    g = gen(520 + H)
+    N, W, C, k = 1, 3, 8, 3
+    x, dout = rnd(g, dt, N, H, W, C), rnd(g, dt, N, H, W, C)
+    w7, dw_old = rnd32(g, 2, k, k, scale=0.3), rnd32(g, 2, k, k)
+    check_spatial(dt, f"rows={N * H}", x, w7, None, dout, dw_old, run_spatial(dt, x, w7, None, dout, dw_old))
+
+
 # ------------------------------------------------------------------------------------------- 6. channel attention, SE
 CA_SHAPES = [(3, 20, 16, 2), (2, 130, 24, 6)]
 # input seeds whose ReLU hidden units are mixed live / dead with one live in every image (asserted in channel_case)
@@ -520,14 +561,14 @@ def run_channel(dt, se, x, w1, b1, w2, b2, act, beta, mul, dout, old):
     gr = {n: up(old[n]) for n in old}
     if se:
         b1d, b2d = up(b1), up(b2)
-        ws = torch.empty(lib().hiseg_se_train_ws(N, C, Cr), device=DEV)
+        ws = workspace(lib().hiseg_se_train_ws(N, C, Cr))
         ok(lib().hiseg_se_train_fwd(HD[dt], ptr(xd), N, HW, C, ptr(w1d), ptr(b1d), Cr, ptr(w2d), ptr(b2d), act,
                                     ptr(ws), ptr(gap), ptr(hpre), ptr(gate), ptr(out), stream()), "se_train_fwd")
         ok(lib().hiseg_se_train_bwd(HD[dt], ptr(xd), N, HW, C, ptr(w1d), Cr, ptr(w2d), act, ptr(gap), ptr(hpre),
                                     ptr(gate), ptr(dd), ptr(dx), ptr(ws), ptr(gr["dw1"]), ptr(gr["db1"]),
                                     ptr(gr["dw2"]), ptr(gr["db2"]), stream()), "se_train_bwd")
     else:
-        ws = torch.empty(lib().hiseg_attn_channel_ws(N, C, Cr), device=DEV)
+        ws = workspace(lib().hiseg_attn_channel_ws(N, C, Cr))
         ok(lib().hiseg_attn_channel_train_fwd(HD[dt], ptr(xd), N, HW, C, ptr(w1d), Cr, ptr(w2d), act, beta, ptr(md),
                                               ptr(ws), ptr(gap), ptr(hpre), ptr(gate), ptr(out), stream()),
            "attn_channel_train_fwd")
@@ -621,7 +662,7 @@ def test_ubf_head(dt, shape, ln, act, beta, ext):
     d.logits, d.bgfg, d.tn = (torch.empty(N, c, H, W, device=DEV) for c in (3, 2, 2))
     d.act, d.act_beta, d.layernorm = act, beta, ln
     rm, rv = up(running[0]), up(running[1])
-    ws = torch.empty(lib().hiseg_ubf_ws(N), device=DEV)
+    ws = workspace(lib().hiseg_ubf_ws(N))
     ok(lib().hiseg_ubf_train_fwd(ctypes.byref(d), 1e-5, 0.1, ptr(rm), ptr(rv), ptr(ws), stream()), "ubf_train_fwd")
     held = d.held()
     tag = f"{shape} ln={ln} act={act} ext={ext}"
@@ -655,13 +696,37 @@ def test_pw2_bwd(dt, Ct, P):
     td, dd, wd = up(tfeat, DTYPES[dt]), up(dtn), up(w)
     dtd = torch.empty_like(td)
     dw, db = up(old_dw), up(old_db)
-    ws = torch.empty(lib().hiseg_pw2_ws(Ct), device=DEV)
+    ws = workspace(lib().hiseg_pw2_ws(Ct))
     ok(lib().hiseg_pw2_bwd(HD[dt], ptr(td), P, Ct, ptr(dd), ptr(wd), ptr(dtd), ptr(ws), ptr(dw), ptr(db), stream()),
        "pw2_bwd")
     (dt64, dw64, db64), (dt32, dw32, db32) = both(O.pw2_bwd, tfeat, dtn, w, old_dw, old_db)
     check("pw2_bwd", dt, f"Ct={Ct} P={P} dt", dtd, dt64, dt32, out_mode(dt))
     check("pw2_bwd", dt, f"Ct={Ct} P={P} dw", dw, dw64, dw32)
     check("pw2_bwd", dt, f"Ct={Ct} P={P} db", db, db64, db32)
+
+
+# the smallest case of each family that owns a workspace, forward and backward, with every oracle check of its test
+WS_CASES = {
+    "spatial": lambda dt: test_spatial_attention(dt, 3, False),
+    "channel": lambda dt: test_channel_attention(dt, CA_SHAPES[0], O.ACT_RELU, 1.0, False),
+    "se": lambda dt: test_squeeze_excite(dt, CA_SHAPES[0]),
+    "ubf-bn-n1": lambda dt: test_ubf_head(dt, (1, 1, 2), 0, O.ACT_RELU, 1.0, False),
+    "ubf-ln-n1": lambda dt: test_ubf_head(dt, (1, 1, 2), 1, O.ACT_RELU, 1.0, False),
+    "ubf-bn-n2": lambda dt: test_ubf_head(dt, (2, 3, 5), 0, O.ACT_RELU, 1.0, False),
+    "ubf-ln-n2": lambda dt: test_ubf_head(dt, (2, 3, 5), 1, O.ACT_RELU, 1.0, False),
+    "pw2": lambda dt: test_pw2_bwd(dt, 8, 7),
+}
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("family", WS_CASES)
+def test_workspace_extents(monkeypatch, dt, family):
+    """The *_ws size is enough and is respected: on a NaN-filled workspace of exactly that size the results still meet
+    the oracle (nothing is read before it is written), and the 64 floats behind it keep their bits."""
+    guarded = GuardedWorkspaces()
+    monkeypatch.setattr(sys.modules[__name__], "workspace", guarded)
+    WS_CASES[family](dt)
+    guarded.assert_guards_untouched()
 
 
 # ------------------------------------------------------------------------------------------- 8. RoIAlign -> output_conv

@@ -1,5 +1,6 @@
 """Plain torch restatements of the non-convolution training kernels (csrc/bn_train.hip, csrc/ln_train.hip,
-csrc/train_ew.hip, csrc/train_head.hip, csrc/roi_align.hip), one function per kernel family.
+csrc/train_ew.hip, csrc/attn_spatial_train.hip, csrc/channel_gate_train.hip, csrc/ubf_train.hip, csrc/roi_align.hip),
+one function per kernel family.
 
 Every function is dtype-generic: it computes in the dtype of its floating inputs.  The GPU tests call each one
 twice on the same inputs (already rounded to the kernel's compute dtype): once in float64 -- the reference -- and
